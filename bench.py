@@ -9,11 +9,15 @@ pick, coarse sync, fine sync, soft demodulation (HIP kernels), host Fano decode 
 tail, coherent subtraction (HIP), second pass, spot records on the host.  With --gpus N every rank
 decodes its own 8 192 segments (weak scaling) and the spot records are gathered on rank 0 over RCCL.
 --config 2 (configs[1]: 1 024 segments x 1 signal at -20 dB) and --config 5 (configs[4]: raw 2.4 Msps
-u8 IQ through the on-GPU decimator) select the other single-GPU configurations; at N=1 the line also
-carries configs[1] as the block "secondary".
+u8 IQ through the on-GPU decimator) select the other single-GPU configurations.
 
-The timed region is never shorter than --min-seconds (default 3 s): if the requested --steps finish
-sooner, the measurement is repeated with proportionally more steps and both numbers are reported.
+A plain run does only what the headline figure needs: it builds the workload, runs the untimed steps,
+times exactly --steps steps, writes the last timed step's spot records with --dump-outputs DIR, and
+prints the line.  Everything else -- the check of the decoded messages against the transmitted ones,
+the warm-cache extra, rooflines, PMC passes and ceilings, the CPU baselines, the other configurations
+("secondary", "tertiary", "configs3_shard", ...), the fan-out check of the multi-rank path -- runs with
+--full.  With --min-seconds S the headline is measured again with proportionally more steps when the
+requested steps finish in less than S seconds (off by default; the --full blocks keep 3 s).
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the fields).
 """
@@ -155,6 +159,39 @@ def synth_raw_gpu(nseg, seed, dev, snr_db=-20.0, noise_lsb=10.0, amp_lsb=None, m
             out[c0:c0 + n.numel(), 1] = (127.5 + zi + nz[:, 1]).round().clamp(0, 255).to(torch.uint8)
         expected.append([synth.expected_text(msg)])
     return raw, expected
+
+
+DUMP_CAP_BYTES = 64 << 20                    # --dump-outputs: at most this much in all
+DUMP_TEXT_FIELDS = ("message", "call", "loc", "pwr")
+
+
+def dump_outputs(path, counts, recs):
+    """--dump-outputs: what the caller of the timed path receives from its last step -- the spot count of every segment
+    and the decoder_results records (wsprd.h:62-74) -- as .npy files in float64 / float32, the records flattened in
+    (segment, spot) order.  The text fields are their bytes (0 = padding) as float32.  Where all segments would exceed
+    DUMP_CAP_BYTES, a fixed sample of segments (seed 0, kept in index order) is written; segments.npy names them."""
+    counts = np.asarray(counts, dtype=np.int64).reshape(-1)
+    nseg, k = recs.shape
+    counts = np.minimum(counts, k)
+    text = sum(recs.dtype[f].shape[0] for f in DUMP_TEXT_FIELDS)
+    per_seg = 3 * 8 + k * (8 + 4 * 4 + 2 * 8 + 8 + 4 * text)          # worst case: every record slot holds a spot
+    sel = np.arange(nseg)
+    if nseg * per_seg > DUMP_CAP_BYTES:
+        sel = np.sort(np.random.default_rng(0).choice(nseg, DUMP_CAP_BYTES // per_seg, replace=False))
+    cnt = counts[sel]
+    flat = recs[sel][np.arange(k)[None, :] < cnt[:, None]]
+    arrays = {"segments": sel.astype(np.float64), "spots_per_segment": cnt.astype(np.float64),
+              "spot_segment": np.repeat(sel, cnt).astype(np.float64),
+              "freq": flat["freq"].astype(np.float64), "jitter": flat["jitter"].astype(np.float64),
+              "cycles": flat["cycles"].astype(np.float64)}
+    for f in ("sync", "snr", "dt", "drift"):
+        arrays[f] = flat[f].astype(np.float32)
+    for f in DUMP_TEXT_FIELDS:
+        arrays[f] = flat[f].view(np.uint8).reshape(len(flat), -1).astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return len(flat)
 
 
 def usable_cpus():
@@ -351,7 +388,9 @@ def child_bench(args, config, steps, warmup, inflight=None, cpu_share=None, spaw
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "WSPR_HOST_THREADS",
                                                              "OMP_NUM_THREADS")}
+    # --full for the correctness figures the blocks quote; its blocks are switched off one by one
     cmd = [sys.executable, os.path.abspath(__file__), "--config", str(config), "--steps", str(steps), "--warmup", str(warmup),
+           "--full", "--min-seconds", str(extra_min_seconds(args)),
            "--no-cpu-baseline", "--no-secondary", "--no-tertiary", "--no-pmc", "--no-share-block", "--no-reference-case",
            "--no-ceilings", "--no-shard-block", "--no-host-entry", "--no-hashtable-block", "--no-kernel-roofline",
            "--no-warm-extra"] + (["--rotate", str(args.rotate)] if args.rotate else [])
@@ -373,6 +412,11 @@ def child_bench(args, config, steps, warmup, inflight=None, cpu_share=None, spaw
     d = json.loads(lines[-1])
     d["child_wall_s"] = time.perf_counter() - t0
     return d
+
+
+def extra_min_seconds(args):
+    """Minimum timed region of the measurements other than the headline (--full): 3 s unless --min-seconds says."""
+    return 3.0 if args.min_seconds is None else args.min_seconds
 
 
 def slim(d):
@@ -606,7 +650,7 @@ def hashtable_block(dev, lanes):
 
 
 def launch_ranks(n):
-    """`python bench.py --gpus N` without a launcher around it: re-executes this script as N ranks of ONE node under
+    """`python bench.py --gpus N` without a launcher around it: runs this script again as N ranks of ONE node under
     torch.distributed.run (one rank per GPU, RCCL over xGMI, rendezvous on 127.0.0.1), each rank with its share of
     the host's CPUs.  Fails loudly if the node has fewer than N GPUs."""
     have = torch.cuda.device_count()
@@ -626,7 +670,10 @@ def launch_ranks(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + argv
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    # a fresh child process (this one has touched the HIP runtime), whose exit status becomes this one's
+    import subprocess
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 def main():
@@ -665,7 +712,16 @@ def main():
                     help="child runs: skip the kernel-level timing sets behind the roofline block (the line then carries no roofline)")
     ap.add_argument("--no-pmc", action="store_true",
                     help="do not measure roofline.traffic with two rocprofv3 --pmc passes (about 40 s); read it from profiles/")
-    ap.add_argument("--min-seconds", type=float, default=3.0, help="minimum length of the timed region")
+    ap.add_argument("--min-seconds", type=float, default=None,
+                    help="minimum length of a timed region: shorter ones are measured again with more steps (headline: off "
+                         "unless given, so that --steps is the number of timed steps; the --full blocks: 3 s unless given)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the check of the decoded messages, the warm-cache extra, "
+                         "rooflines, PMC passes and ceilings, CPU baselines, the other configurations and blocks, the fan-out "
+                         "check (each of them can still be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the spot records of the last timed step as DIR/<field>.npy "
+                         "(float32 / float64, at most 64 MB in all)")
     ap.add_argument("--rotate", type=int, default=None,
                     help="distinct resident batches (other seeds, every signal its own message) a lane rotates through from step "
                          "to step, so that no step finds the previous one's messages in the host's message cache (default: 3, "
@@ -699,7 +755,7 @@ def main():
         torch.set_num_threads(len(cpus))
 
     if "WORLD_SIZE" not in os.environ and (args.gpus > 1 or args.spawn):
-        launch_ranks(args.gpus)                          # does not return: re-executes under torch.distributed.run
+        launch_ranks(args.gpus)                          # does not return: the ranks run under torch.distributed.run
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         sys.exit("bench.py: --gpus %d but WORLD_SIZE=%d: launch one rank per GPU (python bench.py --gpus N spawns them "
@@ -776,10 +832,14 @@ def main():
 
     lanes_primary = inflight
 
-    def measure(config, nseg, steps, warmup, seed, warm=False):
-        """Builds the workload of one configuration and times `steps` steps of it (>= --min-seconds).
-        Cold by construction (round 6): --rotate distinct batches, every signal its own message; a lane's consecutive steps
-        decode different batches.  warm=True: ONE batch of synth.message_for texts on every step (the round-5 shape)."""
+    def measure(config, nseg, steps, warmup, seed, warm=False, min_seconds=None, check=True, dump_dir=None):
+        """Builds the workload of one configuration and times `steps` steps of it (>= min_seconds, default: the --full
+        blocks' minimum).  Cold by construction (round 6): --rotate distinct batches, every signal its own message; a lane's
+        consecutive steps decode different batches.  warm=True: ONE batch of synth.message_for texts on every step (the
+        round-5 shape).  check: compare the last step's messages with the transmitted ones (decoded_ok, false_decodes).
+        dump_dir: write the last step's spot records there (dump_outputs)."""
+        if min_seconds is None:
+            min_seconds = extra_min_seconds(args)
         fast_old = None
         inflight = lanes_primary if config == args.config else (min(args.inflight, 6) if args.inflight else default_inflight(config))
         nsig_of = {2: 1, 3: 10, 4: 1, 5: 1}[config]
@@ -905,27 +965,36 @@ def main():
         elapsed, (gathered, timings, lastk) = timed(steps)
         first = {"steps": steps, "seconds": elapsed}
         n_timed = steps
-        if elapsed < args.min_seconds:
+        if elapsed < min_seconds:
             # too short to trust: repeat with enough steps for the minimum region (every rank takes the same
             # decision: `elapsed` is the maximum over ranks)
-            n_timed = int(np.ceil(steps * args.min_seconds / max(elapsed, 1e-6) * 1.1))
+            n_timed = int(np.ceil(steps * min_seconds / max(elapsed, 1e-6) * 1.1))
             elapsed, (gathered, timings, lastk) = timed(n_timed)
-        # correctness of what was timed: every segment's message must be the transmitted one
         lastk, lastb = lastk
         dec = decs[lastk]                                                        # the last step's results ...
         I, Q, expected = batches[lastb] if batches else (I, Q, expected)         # ... and the batch it decoded
         del batches
-        got = [[s.message.decode() for s in dec.spots(i)] for i in range(nseg)]
-        n_sent = sum(len(e) for e in expected)
-        n_ok = sum(len(set(expected[i]) & set(got[i])) for i in range(nseg))
-        n_false = sum(len([m for m in got[i] if m not in expected[i]]) for i in range(nseg))
+        if dump_dir is not None and rank == 0:
+            # what the caller of the timed path received from the last step: every rank's records where they were gathered
+            if gathered is not None:
+                cnt, recs = gathered[0].numpy(), gathered[1].numpy()
+            else:
+                cnt, recs = np.frombuffer(dec.nres, dtype=np.int32), np.frombuffer(dec.out, dtype=np.uint8)
+            dump_outputs(dump_dir, cnt, recs.reshape(-1).view(np.dtype(w.decoder_results)).reshape(-1, dec.max_results))
+        got, n_ok, n_sent, n_false = None, None, None, None
+        if check:
+            # correctness of what was timed: every segment's message must be the transmitted one
+            got = [[s.message.decode() for s in dec.spots(i)] for i in range(nseg)]
+            n_sent = sum(len(e) for e in expected)
+            n_ok = sum(len(set(expected[i]) & set(got[i])) for i in range(nseg))
+            n_false = sum(len([m for m in got[i] if m not in expected[i]]) for i in range(nseg))
         total_spots = int(gathered[0].sum()) if gathered is not None else dec.total_spots()
         if fast_old is not None:
             L.wspr_set_fano_fast_budget(C.c_uint(fast_old))
         return {"config": config, "nseg": nseg, "I": I, "Q": Q, "raw": raw, "expected": expected, "got": got,
                 "workload": workload, "steps": n_timed, "elapsed": elapsed, "first_try": first, "untimed": untimed, "slots": slots_used, "inflight": inflight,
                 "value": world * nseg * n_timed / elapsed, "ms_per_step": elapsed / n_timed * 1e3,
-                "decoded_ok": "%d/%d" % (n_ok, n_sent), "false_decodes": n_false, "spots_total": total_spots,
+                "decoded_ok": "%d/%d" % (n_ok, n_sent) if check else None, "false_decodes": n_false, "spots_total": total_spots,
                 "spots_own": dec.total_spots(),
                 "timings": dict(timings, message_cache_hit_rate=(timings.get("message_cache_hits", 0.0) /
                                                                   max(1.0, timings.get("message_cache_lookups", 0.0)))),
@@ -944,10 +1013,11 @@ def main():
         now = time.perf_counter()
         walls[name] = round(now - t_prog, 1)
         t_prog = now
-    m = measure(args.config, nseg, args.steps, args.warmup, rank)
+    m = measure(args.config, nseg, args.steps, args.warmup, rank, min_seconds=args.min_seconds or 0.0, check=args.full,
+                dump_dir=args.dump_outputs)
     lap("headline (synthesis, untimed and timed steps)")
     warm_extra = None
-    if not args.no_warm_extra and args.config != 5 and args.rotate != 1 and world == 1 and not use_dist:
+    if args.full and not args.no_warm_extra and args.config != 5 and args.rotate != 1 and world == 1 and not use_dist:
         # the round-5 shape beside the cold figure (labelled extra, never `value`): ONE batch of synth.message_for texts
         # decoded on every step, so every message after the first step comes out of the host's per-thread cache
         keep = {k: m[k] for k in ("I", "Q")}
@@ -973,7 +1043,7 @@ def main():
         ranks_info = [None] * world
         dist.all_gather_object(ranks_info, mine)
     fanout = None
-    if use_dist and args.config != 5:
+    if args.full and use_dist and args.config != 5:
         # ---- real-input fan-out, untimed (the reference's callers hold the IQ in ONE place,
         # rtlsdr_wsprd.c:316, :689): rank 0 scatters rows of ITS batch over RCCL (grouped send/recv of 360 000 B
         # per segment), every rank decodes the rows it received, the records come back in global order and
@@ -1000,7 +1070,7 @@ def main():
     if rank == 0:
         I, Q = m["I"], m["Q"]
         roof = None
-        if not args.no_kernel_roofline:
+        if args.full and not args.no_kernel_roofline:
             # ---- kernel-level roofline of the FFT+sync stage, HIP events on the launch stream.  The timing sets and the
             # calibration kernels are entry points of the LAB library (include/wspr_mi355x_bench.h; the same kernels from
             # the same sources: the product exports no benchmark); `value` above was measured on the product library.
@@ -1112,7 +1182,7 @@ def main():
         if args.config == 5 and roof is not None:
             roof["front_end_K0"] = k0_report(w.lab(), m, world == 1 and not args.no_cpu_baseline)
             cpu = roof["front_end_K0"].pop("cpu_baseline", None)
-        if world == 1 and not args.no_cpu_baseline and args.config != 5:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.config != 5:
             cnt = min(nseg, 512)
             Ih, Qh = I[:cnt].cpu().numpy(), Q[:cnt].cpu().numpy()
             cpu, cpu_msgs = cpu_baseline(Ih, Qh, m["expected"][:cnt], 25.0 if args.config == 2 else 14.0)
@@ -1120,7 +1190,7 @@ def main():
             cpu["gpu_equals_cpu_spots"] = "%d/%d segments" % (same, len(cpu_msgs))
         lap("cpu_baseline")
         secondary = None
-        if world == 1 and args.config == 3 and not args.no_secondary and not use_dist:
+        if args.full and world == 1 and args.config == 3 and not args.no_secondary and not use_dist:
             del I, Q
             m["I"] = m["Q"] = None
             torch.cuda.empty_cache()
@@ -1132,7 +1202,7 @@ def main():
                          "false_decodes": m2["false_decodes"], "stage_ms_last_step": m2["timings"]}
         lap("secondary")
         tertiary = None
-        if world == 1 and args.config == 3 and not args.no_tertiary and not use_dist:
+        if args.full and world == 1 and args.config == 3 and not args.no_tertiary and not use_dist:
             # configs[4] (raw 2.4 Msps input through the on-GPU decimator) rides along in the default line: its
             # throughput, K0's roofline and the decimator's CPU baseline
             m["I"] = m["Q"] = None
@@ -1148,7 +1218,7 @@ def main():
             torch.cuda.empty_cache()
         lap("tertiary")
         shard = None
-        if world == 1 and args.config == 3 and not args.no_shard_block and not use_dist:
+        if args.full and world == 1 and args.config == 3 and not args.no_shard_block and not use_dist:
             # configs[3]'s per-rank shard (8 192 single-signal segments): in this process with the whole host, then in
             # children with a rank's CPU share and as a world-1 RCCL rank
             I = Q = None
@@ -1165,7 +1235,7 @@ def main():
             shard = shard_block(args, full)
         lap("configs3_shard")
         host_entry = None
-        if world == 1 and args.config == 3 and not args.no_host_entry and not use_dist:
+        if args.full and world == 1 and args.config == 3 and not args.no_host_entry and not use_dist:
             I = Q = None
             m["I"] = m["Q"] = None
             torch.cuda.empty_cache()
@@ -1173,7 +1243,7 @@ def main():
             host_entry = host_entry_block(dev, lanes[:12], m["value"])
         lap("host_entry")
         hashtable = None
-        if world == 1 and args.config == 3 and not args.no_hashtable_block and not use_dist:
+        if args.full and world == 1 and args.config == 3 and not args.no_hashtable_block and not use_dist:
             torch.cuda.empty_cache()
             hashtable = hashtable_block(dev, lanes)
         lap("usehashtable_batch")
@@ -1204,7 +1274,7 @@ def main():
             "configs3_shard": shard, "host_entry": host_entry, "usehashtable_batch": hashtable,
             "fanout_check": fanout, "ranks": ranks_info if use_dist else None,
         }
-        if world == 1 and not use_dist and args.config == 3:
+        if args.full and world == 1 and not use_dist and args.config == 3:
             if not args.no_reference_case:
                 out["reference_case_configs0"] = reference_case_block(not args.no_cpu_baseline)
             if not args.no_share_block:

@@ -1,6 +1,6 @@
 cd "$GRAFT_REPO_ROOT"
 (for i in $(seq 1 70); do echo "s$i $(rocm-smi --showclocks --showpower 2>/dev/null | grep -i "sclk\|mclk\|Package Power" | sed "s/GPU\[0\]\s*: //" | tr "\n" " ")"; sleep 0.4; done > /tmp/clk5.txt) &
-python bench.py --config 5 --no-cpu-baseline --no-pmc --min-seconds 6 2>/dev/null | python tools/c5_line.py config5
+python bench.py --full --config 5 --no-cpu-baseline --no-pmc --min-seconds 6 2>/dev/null | python tools/c5_line.py config5
 wait
 python - <<'PY'
 import re

@@ -6,7 +6,7 @@ envs=("$@")
 for round in 1 2; do
 for e in "${envs[@]}"; do
   [ "$e" = "-" ] && e="WSPR_NOTHING=1"
-  env $e python bench.py --config $cfg --no-cpu-baseline --no-secondary --no-tertiary --no-pmc --no-share-block --no-reference-case --no-ceilings 2>/dev/null | python -c "
+  env $e python bench.py --full --config $cfg --no-cpu-baseline --no-secondary --no-tertiary --no-pmc --no-share-block --no-reference-case --no-ceilings 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -8,7 +8,7 @@ showp='import sys,json
 d=json.loads(sys.stdin.read()); b=d["pcie_bound_segments_per_s"]
 print("probe", d["config"], round(d["resident"]["segments_per_s"]), round(d["host_pageable"]["segments_per_s"]), round(d["host_pageable"]["segments_per_s"]/b,3), round(d["host_pinned"]["segments_per_s"]), round(d["host_pinned"]["segments_per_s"]/b,3))'
 for i in 1 2; do
-  python bench.py --steps 4 --warmup 1 --min-seconds 1 $f 2>/dev/null | python -c "$show"
+  python bench.py --full --steps 4 --warmup 1 --min-seconds 1 $f 2>/dev/null | python -c "$show"
   python tools/host_entry_probe.py 2 2>/dev/null | tail -1 | python -c "$showp"
 done
 python tools/host_entry_probe.py 3 2>/dev/null | tail -1 | python -c "$showp"

@@ -1,6 +1,6 @@
 cd "$GRAFT_REPO_ROOT"
 for round in 1 2; do for cfg in 3 2; do for s in 3 4 6 8; do
-WSPR_SLOTS=$s python bench.py --config $cfg --slots $s --inflight 1 --no-cpu-baseline --no-secondary --no-tertiary --no-pmc --no-share-block --no-reference-case --no-ceilings 2>/dev/null | python -c "
+WSPR_SLOTS=$s python bench.py --full --config $cfg --slots $s --inflight 1 --no-cpu-baseline --no-secondary --no-tertiary --no-pmc --no-share-block --no-reference-case --no-ceilings 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -6,7 +6,7 @@ shapes=("$@")
 for round in 1 2; do
 for shape in "${shapes[@]}"; do
   set -- $shape
-  python bench.py --config $cfg --slots $1 --inflight $2 --no-cpu-baseline --no-secondary --no-tertiary --no-pmc --no-share-block --no-reference-case --no-ceilings 2>/dev/null | python -c "
+  python bench.py --full --config $cfg --slots $1 --inflight $2 --no-cpu-baseline --no-secondary --no-tertiary --no-pmc --no-share-block --no-reference-case --no-ceilings 2>/dev/null | python -c "
 import sys,json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -7,7 +7,7 @@ for share in 0 2; do
   for inf in 1 2 4 8 12; do
     extra=""; [ "$share" != 0 ] && extra="--cpu-share $share"
     echo "== share $share inflight $inf" >&2
-    timeout 300 python bench.py --config 4 --steps 20 --warmup 4 --inflight $inf $extra $slim 2>/dev/null | grep '^{' | \
+    timeout 300 python bench.py --full --config 4 --steps 20 --warmup 4 --inflight $inf $extra $slim 2>/dev/null | grep '^{' | \
       python -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({'share':$share,'inflight':$inf,'value':d['value'],'ms_per_step':d['ms_per_step'],'decoded_ok':d['decoded_ok'],'stage':d['stage_ms_last_step'],'workers':d['host_pool_workers']}))" >> "$out"
     tail -1 "$out" >&2
   done
