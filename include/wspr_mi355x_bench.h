@@ -41,7 +41,9 @@ typedef struct wspr_cand_trace {
     unsigned cycles;
     unsigned char first_symbols[162];
     unsigned char decdata[11];
-    unsigned char pad[3];
+    unsigned char stop;         /* the pass left the candidate loop here: 1 the decode did not re-encode (:786-788),
+                                   2 its locator is "A000AA" (:791-793); 0 otherwise (was padding: the size is unchanged) */
+    unsigned char pad[2];
 } wspr_cand_trace;
 typedef struct wspr_trace {
     int passes_run;

@@ -424,6 +424,11 @@ void orc_subtract_simple(float *id, float *qd, long np, float f0, int shift, flo
  * options.usehashtable is set.  The fftw_wisdom.dat side effect is FFTW-specific and not restated. */
 int orc_wspr_decode(float *idat, float *qdat, int samples, orc_options opt,
                     orc_spot *spots, int *n_results, orc_trace *tr) {
+    return orc_wspr_decode_stops(idat, qdat, samples, opt, spots, n_results, tr, NULL);
+}
+
+int orc_wspr_decode_stops(float *idat, float *qdat, int samples, orc_options opt,
+                          orc_spot *spots, int *n_results, orc_trace *tr, orc_stops *st) {
     const float minsync1 = 0.10f;
     float minsync2 = 0.12f;
     const int iifac = 3, symfac = 50;
@@ -469,6 +474,7 @@ int orc_wspr_decode(float *idat, float *qdat, int samples, orc_options opt,
     memset(decdata, 0, sizeof decdata);
     memset(message, 0, sizeof message);
     if (tr) { memset(tr, 0, sizeof *tr); tr->blocks = blocks; }
+    if (st) memset(st, 0, sizeof *st);
 
     for (int ipass = 0; ipass < opt.npasses; ipass++) {
         if (ipass == 1 && uniques == 0) break;
@@ -569,10 +575,15 @@ int orc_wspr_decode(float *idat, float *qdat, int samples, orc_options opt,
                         if (tr) tr->subtracted[ipass][j] = 1;
                     } else {
                         stop = 1;         /* wsprd.c:787 leaves the candidate loop */
+                        if (st && ipass < ORC_TRACE_PASSES) { st->reason[ipass] = 1; st->cand[ipass] = j; }
                         continue;
                     }
                 }
-                if (!strcmp(loc, "A000AA")) { stop = 1; continue; }   /* wsprd.c:792 */
+                if (!strcmp(loc, "A000AA")) {                         /* wsprd.c:792 */
+                    stop = 1;
+                    if (st && ipass < ORC_TRACE_PASSES) { st->reason[ipass] = 2; st->cand[ipass] = j; }
+                    continue;
+                }
 
                 int dupe = 0;
                 for (int i = 0; i < uniques; i++)

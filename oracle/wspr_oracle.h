@@ -92,6 +92,12 @@ typedef struct {
     long     fano_cycles_total;                        /* sum over all calls  */
 } orc_trace;
 
+/* Where each pass left the candidate loop (tests only; a record of its own so that orc_trace keeps its size). */
+typedef struct {
+    int reason[ORC_TRACE_PASSES];   /* 0 ran out of candidates, 1 re-encode failed (wsprd.c:786-788), 2 "A000AA" (:791-793) */
+    int cand[ORC_TRACE_PASSES];     /* the candidate it stopped at (reason != 0) */
+} orc_stops;
+
 /* ---- message layer ------------------------------------------------------ */
 uint32_t orc_nhash(const void *key, size_t length, uint32_t initval);
 char     orc_call_char_code(char ch);
@@ -141,6 +147,9 @@ void orc_subtract_simple(float *id, float *qd, long np, float f0, int shift, flo
                          const unsigned char *channel_symbols);
 int  orc_wspr_decode(float *idat, float *qdat, int samples, orc_options opt,
                      orc_spot *spots, int *n_results, orc_trace *trace);
+/* the same, also filling stops (may be NULL) */
+int  orc_wspr_decode_stops(float *idat, float *qdat, int samples, orc_options opt,
+                           orc_spot *spots, int *n_results, orc_trace *trace, orc_stops *stops);
 
 /* ---- front end ---------------------------------------------------------- */
 typedef struct orc_decim_state orc_decim_state;

@@ -48,15 +48,15 @@ class cand(C.Structure):                     # wsprd/wsprd.h:54-60
 TRACE_PASSES = 3
 
 
-class cand_trace(C.Structure):               # include/wspr_mi355x.h: wspr_cand_trace
+class cand_trace(C.Structure):               # include/wspr_mi355x_bench.h: wspr_cand_trace
     _fields_ = [("visited", C.c_int), ("mode0_shift", C.c_int), ("mode0_sync", C.c_float),
                 ("freq", C.c_float), ("shift", C.c_int), ("drift", C.c_float), ("sync", C.c_float),
                 ("attempts", C.c_int), ("fano_calls", C.c_int), ("first_sync", C.c_float), ("first_rms", C.c_float),
                 ("decoded", C.c_int), ("subtracted", C.c_int), ("jitter", C.c_int), ("cycles", C.c_uint),
-                ("first_symbols", C.c_ubyte * NSYM), ("decdata", C.c_ubyte * 11), ("pad", C.c_ubyte * 3)]
+                ("first_symbols", C.c_ubyte * NSYM), ("decdata", C.c_ubyte * 11), ("stop", C.c_ubyte), ("pad", C.c_ubyte * 2)]
 
 
-class trace(C.Structure):                    # include/wspr_mi355x.h: wspr_trace
+class trace(C.Structure):                    # include/wspr_mi355x_bench.h: wspr_trace
     _fields_ = [("passes_run", C.c_int), ("npk", C.c_int * TRACE_PASSES), ("n_visited", C.c_int * TRACE_PASSES),
                 ("cand", (cand_trace * MAX_CANDIDATES) * TRACE_PASSES)]
 

@@ -828,10 +828,15 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
                 cut = true;            // the IQ changes: later candidates of this window are redone
             } else {
                 stopped[s] = 1;                      // wsprd.c:786-788: leaves the candidate loop
+                if (tc) tc->stop = 1;
                 continue;
             }
         }
-        if (!strcmp(loc, "A000AA")) { stopped[s] = 1; continue; }      // wsprd.c:792-793
+        if (!strcmp(loc, "A000AA")) {                                   // wsprd.c:792-793
+            stopped[s] = 1;
+            if (tc) tc->stop = 2;
+            continue;
+        }
         bool dupe = false;
         for (int u = 0; u < bk.uniques; ++u)
             if (!strcmp(callsign, bk.allcalls[u]) && fabs(w.fine.freq - bk.allfreqs[u]) < 3.0) dupe = true;

@@ -67,6 +67,10 @@ class Trace(C.Structure):
                 ("fano_cycles_total", C.c_long)]
 
 
+class Stops(C.Structure):              # oracle/wspr_oracle.h: orc_stops
+    _fields_ = [("reason", C.c_int * P), ("cand", C.c_int * P)]
+
+
 def default_options(freq=144489000, npasses=2, subtraction=1, quickmode=0):
     """Decoder defaults of rtlsdr_wsprd.c:357-362; dial 144.489 MHz = the '2m' band."""
     return Options(freq=freq, quickmode=quickmode, usehashtable=0,
@@ -92,6 +96,9 @@ def lib():
         L.orc_wspr_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, Options,
                                       C.c_void_p, C.c_void_p, C.c_void_p]
         L.orc_wspr_decode.restype = C.c_int
+        L.orc_wspr_decode_stops.argtypes = [C.c_void_p, C.c_void_p, C.c_int, Options,
+                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.orc_wspr_decode_stops.restype = C.c_int
         L.orc_nhash.restype = C.c_uint32
         L.orc_nhash.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32]
         L.orc_pack_call.restype = C.c_ulong
@@ -152,7 +159,8 @@ def read_iq_file(path):
 
 
 def decode(I, Q, samples=None, opt=None, trace=False):
-    """Run the oracle decoder on copies of I/Q. Returns (spots, residual I, Q[, trace])."""
+    """Run the oracle decoder on copies of I/Q. Returns (spots, residual I, Q[, trace]); the trace also carries, per
+    pass, where the candidate loop stopped early (stop_reason 0 none / 1 re-encode failed / 2 "A000AA", stop_cand)."""
     L = lib()
     I = np.ascontiguousarray(I, dtype=np.float32).copy()
     Q = np.ascontiguousarray(Q, dtype=np.float32).copy()
@@ -161,8 +169,13 @@ def decode(I, Q, samples=None, opt=None, trace=False):
     spots = (Spot * 100)()
     nres = C.c_int(0)
     tr = Trace() if trace else None
-    L.orc_wspr_decode(ptr(I), ptr(Q), n, opt, C.addressof(spots), C.addressof(nres),
-                      C.addressof(tr) if trace else None)
+    if trace:
+        st = Stops()
+        L.orc_wspr_decode_stops(ptr(I), ptr(Q), n, opt, C.addressof(spots), C.addressof(nres), C.addressof(tr),
+                                C.addressof(st))
+        tr.stop_reason, tr.stop_cand = list(st.reason), list(st.cand)
+    else:
+        L.orc_wspr_decode(ptr(I), ptr(Q), n, opt, C.addressof(spots), C.addressof(nres), None)
     out = [spots[i] for i in range(nres.value)]
     return (out, I, Q, tr) if trace else (out, I, Q)
 

@@ -104,6 +104,26 @@ def test_c_header_compiles_and_agrees_on_sizes(tmp_path):
     assert subprocess.run([str(exe)], capture_output=True, text=True).stdout.split() == ["40", "80", "20", "28", "76"]
 
 
+def test_trace_mirrors_agree_with_the_c_structs(tmp_path):
+    """The per-candidate traces of the product (wspr_trace) and of the oracle (orc_trace, orc_stops) as the ctypes mirrors
+    see them.  The early-exit mark sits in what was padding of wspr_cand_trace: neither trace changed its size, so a
+    caller built against the earlier layout still hands over buffers that are large enough."""
+    import oracle_lib as ol
+    src = tmp_path / "t.c"
+    src.write_text('#include "wspr_mi355x_bench.h"\n#include "wspr_oracle.h"\n#include <stdio.h>\n#include <stddef.h>\n'
+                   'int main(void){printf("%zu %zu %zu %zu %zu %zu %zu\\n", sizeof(wspr_cand_trace),'
+                   'offsetof(wspr_cand_trace, stop), offsetof(wspr_cand_trace, pad), sizeof(wspr_trace), sizeof(orc_trace),'
+                   'sizeof(orc_stops), offsetof(orc_stops, cand));return 0;}\n')
+    exe = tmp_path / "t"
+    subprocess.run(["gcc", "-std=gnu17", "-I", os.path.join(ROOT, "include"), "-I", os.path.join(ROOT, "oracle"), str(src),
+                    "-o", str(exe)], check=True)
+    got = [int(x) for x in subprocess.run([str(exe)], capture_output=True, text=True).stdout.split()]
+    assert got == [C.sizeof(w.cand_trace), w.cand_trace.stop.offset, w.cand_trace.pad.offset, C.sizeof(w.trace),
+                   C.sizeof(ol.Trace), C.sizeof(ol.Stops), ol.Stops.cand.offset]
+    assert w.cand_trace.stop.offset == w.cand_trace.decdata.offset + 11 and C.sizeof(w.cand_trace) == 236
+    assert C.sizeof(w.trace) == 4 + 2 * 4 * 3 + 3 * 200 * 236 and C.sizeof(ol.Trace) == 171184
+
+
 def test_device_entry_points_fail_loudly_without_gpu():
     """No CPU fallback: on a box without a HIP device the decode returns an error, not spots."""
     import numpy as np

@@ -65,6 +65,7 @@ def _run_with(env, sets):
                                  {"WSPR_K3_KERNEL": "waves", "WSPR_K1_FUSED": "0", "WSPR_SLOTS": "1"}],
                          ids=lambda e: ",".join("%s=%s" % kv for kv in e.items()))
 def test_trace_under_the_kept_environment_switches(env):
-    """Every alternative kernel / placement that stays selectable must give the same per-candidate values."""
+    """Every alternative kernel / placement that stays selectable must give the same per-candidate values, the
+    early exits of the candidate loop (tests/payloads.py) included."""
     os.environ.setdefault("WSPR_TRACE_SCENES", "20")
-    _run_with(env, ["parity", "scenes"])
+    _run_with(env, ["parity", "scenes", "loopexits"])

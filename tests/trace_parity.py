@@ -4,6 +4,7 @@ enters, decoded or not.  Used by tests/test_gpu_trace.py in-process and, as a sc
 the library's environment switches (they are read once per process):
 
     python tests/trace_parity.py parity scenes        -> exit 0 if every field of every visited candidate is equal
+    (sets: parity, scenes, loopexits (the crafted early-exit scenes of tests/payloads.py), config3)
 """
 import os
 import sys
@@ -14,6 +15,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 NS = 45000
+
+
+def stops_of(gt):
+    """(stop_reason, stop_cand) per pass of a product trace, from the per-candidate stop marks."""
+    reason, cand = [0] * len(gt.n_visited), [0] * len(gt.n_visited)
+    for p in range(gt.passes_run):
+        for j in range(gt.n_visited[p]):
+            if gt.cand[p][j].stop:
+                reason[p], cand[p] = gt.cand[p][j].stop, j
+    return reason, cand
 
 
 def compare_segment(gt, ot, where):
@@ -35,9 +46,10 @@ def compare_segment(gt, ot, where):
             assert (g.decoded, g.subtracted) == (ot.decoded[p][j], ot.subtracted[p][j]), at
             if g.decoded:
                 assert g.cycles == ot.fano_cycles[p][j] and bytes(g.decdata) == bytes(ot.decdata[p][j]), at
+            assert g.stop == (ot.stop_reason[p] if j == ot.stop_cand[p] else 0), at                       # early exit
             n += 1
         for j in range(ot.n_visited[p], 200):
-            assert gt.cand[p][j].visited == 0, (where, p, j)
+            assert gt.cand[p][j].visited == 0 and gt.cand[p][j].stop == 0, (where, p, j)
     return n
 
 
@@ -77,6 +89,11 @@ def main(argv):
             from test_gpu_parity import random_scenes
             I, Q = random_scenes(int(os.environ.get("WSPR_TRACE_SCENES", "40")))
             print(what, check(I, Q, w, ol, None, what), flush=True)
+        elif what == "loopexits":
+            import payloads
+            _, Is, Qs = zip(*payloads.loop_exit_scenes())
+            for o in (dict(), dict(npasses=1)):
+                print(what, o, check(np.stack(Is), np.stack(Qs), w, ol, o, what), flush=True)
         elif what == "config3":
             import bench
             dev = torch.device("cuda", 0)
