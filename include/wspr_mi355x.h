@@ -366,6 +366,30 @@ unsigned wspr_set_fano_fast_budget(unsigned cycles_per_bit);
  * host threads or the pipeline's previous batch met more than one time-out per ten segments (a crowded band),
  * the host otherwise (single calls always).  Results are identical in every mode.  Returns the previous value. */
 int wspr_set_fano_device_mode(int mode);
+/* Arithmetic of the signal-processing stages, process-wide (like wspr_set_fano_device_mode()).
+ *   WSPR_ARITH_EXACT (the default): every float sum and product separately rounded in the reference's order, i.e.
+ *     what the reference's x86-64 build computes without FMA; bit-exact against that evaluation.
+ *   WSPR_ARITH_CONTRACTED: each sum of products that clang's front end contracts in wsprd/wsprd.c under its default
+ *     -ffp-contract=on becomes the fused multiply-add it makes there, and nothing else.  clang fuses within one
+ *     expression, the LEFT product first: a*b + c*d -> fma(a, b, c*d), (acc + x*c) + y*s -> fma(y, s, fma(x, c, acc)),
+ *     acc - x*s -> fma(-x, s, acc).  The sites, by wsprd.c line: 151 (frequency hypotheses), 180-187 (phasor
+ *     recurrences), 200-207 (matched-filter sums), 211-214 (tone amplitudes), 249 (soft-symbol normalisation),
+ *     378-379 / 388-389 / 408-409 (subtract_signal2: mixing, low-pass filter, write-back), 551 (FFT powers); the
+ *     integer-valued products of 516, 571, 616, 663 and 754 are exact either way.  The FFT, the receiver front end
+ *     and everything integer are the same in both modes, and subtract_signal() stays exact in both.
+ *   The contracted mode CHANGES RESULTS, a little (tools/contract_robustness.py, profiles/contracted_robustness.json,
+ *   against the exact mode): over 3 000 random scenes one of 6 880 spots is lost and one moves its dt by 64 ms (beyond
+ *   the 10 ms tolerance); no call/loc/pwr changes, SNR moves by < 1e-5 dB, frequency by <= 0.1 Hz.
+ *   No mode reproduces the reference's arm64 binary bit for bit: its Makefile's `CC ?= clang` leaves make's default
+ *   `cc` in place, and gcc's gnu17 default -ffp-contract=fast fuses after optimisation by no rule the source text
+ *   states.  The clang rule above is the one contraction the source defines and anyone can reproduce.
+ * Every wspr_decode*() and wspr_session_decode*() call, sync_and_demodulate() and subtract_signal2() reads the mode
+ * once, on entry, and uses it throughout (all slots, node worker threads and hash rounds of the call); a
+ * WSPR_HASH_REVISIT call must run under the mode of the call it completes.  Returns the previous mode, or -1 (nothing
+ * changed) for any other value. */
+#define WSPR_ARITH_EXACT      0
+#define WSPR_ARITH_CONTRACTED 1
+int wspr_set_arithmetic(int mode);
 /* Library / device description, e.g. for bench logs. */
 const char *wspr_mi355x_version(void);
 int wspr_device_ready(void);        /* 1 if a HIP device and the kernels are usable */

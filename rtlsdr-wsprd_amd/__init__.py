@@ -61,6 +61,9 @@ class trace(C.Structure):                    # include/wspr_mi355x_bench.h: wspr
                 ("cand", (cand_trace * MAX_CANDIDATES) * TRACE_PASSES)]
 
 
+WSPR_ARITH_EXACT, WSPR_ARITH_CONTRACTED = 0, 1    # include/wspr_mi355x.h: wspr_set_arithmetic()
+
+
 def default_options(freq=144489000, npasses=2, subtraction=1, quickmode=0):
     """initDecoder_options(), rtlsdr_wsprd.c:357-362."""
     return decoder_options(freq=freq, quickmode=quickmode, usehashtable=0,
@@ -105,6 +108,8 @@ def _bind(path):
     L.wspr_unpin_host_buffer.argtypes = [C.c_void_p]
     L.wspr_release_buffers.restype = C.c_size_t
     L.wspr_set_fano_fast_budget.restype = C.c_uint
+    L.wspr_set_arithmetic.argtypes = [C.c_int]
+    L.wspr_set_arithmetic.restype = C.c_int
     L.nhash.restype = C.c_uint32
     L.nhash.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32]
     L.pack_call.restype = C.c_ulong
@@ -161,6 +166,13 @@ def lab():
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def wspr_set_arithmetic(mode, library=None):
+    """Process-wide arithmetic of the signal-processing stages (include/wspr_mi355x.h): WSPR_ARITH_EXACT (default) or
+    WSPR_ARITH_CONTRACTED.  Returns the previous mode, or -1 (nothing changed) for any other value.  The product and
+    the lab library each keep their own setting: `library` (default: lib()) is the one set."""
+    return (library or lib()).wspr_set_arithmetic(int(mode))
 
 
 def get_wspr_channel_symbols(message):

@@ -69,6 +69,7 @@ int current_device_or_0() {
     return dev;
 }
 struct LaneTurn {                                  // the calling thread's lane of the current device
+    wspr::ArithScope arith;                        // the outermost entry point reads wspr_set_arithmetic() here, once
     std::unique_lock<std::recursive_mutex> hold;
     LaneTurn() : hold(lane_turn_of(current_device_or_0(), Context::lane())) {}
 };
@@ -103,7 +104,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
     const int nslots = (nseg >= 128) ? Context::slot_cap() : 1;
     Context::note_slots_used(nslots);
     Context& c0 = Context::get();
-    const int dev = c0.device(), lane = Context::lane();
+    const int dev = c0.device(), lane = Context::lane(), arith = wspr::call_arith();
     struct Share { int lo, hi; };
     std::vector<Share> share(nslots);
     for (int g = 0; g < nslots; ++g) share[g] = {(int)((long)nseg * g / nslots), (int)((long)nseg * (g + 1) / nslots)};
@@ -116,6 +117,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
         for (int g = 0; g < nslots; ++g)
             th.emplace_back([&, g] {
                 try {
+                    wspr::ArithScope call_mode(arith);
                     if (hipSetDevice(dev) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
                     Context::bind_lane(lane);
                     fn(g, Context::slot(g));
@@ -234,12 +236,13 @@ int decode_hashed(int nseg, int samples, const decoder_options& options, decoder
     // same segments, samples and slot layout (wspr_set_thread_slots / a node-level share in between change the shares)
     const int nslots_now = (nseg >= 128) ? Context::slot_cap() : 1;
     if (revisit && !(t_hash && t_hash->valid && (int)t_hash->log.size() == nseg && t_hash->seg0 == seg_index0 &&
-                     t_hash->samples == samples && t_hash->nslots == nslots_now))
+                     t_hash->samples == samples && t_hash->nslots == nslots_now && t_hash->arith == wspr::call_arith()))
         throw std::runtime_error("WSPR_HASH_REVISIT without a matching, completed previous call on this thread");
     if (!revisit) {
         t_hash.reset(new wspr::HashBatch);
         t_hash->load_file();
         t_hash->seg0 = seg_index0;
+        t_hash->arith = wspr::call_arith();
         t_hash->resize(nseg);
     }
     wspr::HashBatch& hb = *t_hash;
@@ -497,7 +500,8 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
     if (options.usehashtable && nseg > 1)                // ordered by definition: nothing to spread
         return wspr_decode_batch(idat, qdat, nseg, samples, seg_stride, options, decodes, max_results, n_results, 0);
     NodeShareGuard share(ndevices);
-    const int lane0 = Context::lane();
+    wspr::ArithScope call_mode;
+    const int lane0 = Context::lane(), arith = wspr::call_arith();
     int home = 0;
     (void)hipGetDevice(&home);
     std::vector<int> rcs(ndevices, 0);
@@ -507,6 +511,7 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
         wspr_shard_range(nseg, k, ndevices, &lo, &hi);
         if (hi <= lo) continue;
         th.emplace_back([=, &rcs] {
+            wspr::ArithScope worker_mode(arith);
             if (hipSetDevice(k % count) != hipSuccess) {
                 rcs[k] = -1;
                 for (int s = lo; s < hi; ++s) n_results[s] = 0;
@@ -559,7 +564,8 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
         return rc;
     }
     NodeShareGuard share(ndevices);
-    const int lane0 = Context::lane();
+    wspr::ArithScope call_mode;
+    const int lane0 = Context::lane(), arith = wspr::call_arith();
     std::vector<int> rcs(ndevices, 0);
     std::vector<std::thread> th;
     for (int k = 0; k < ndevices; ++k) {
@@ -567,6 +573,7 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
         wspr_shard_range(nseg, k, ndevices, &lo, &hi);
         if (hi <= lo) continue;
         th.emplace_back([=, &rcs] {
+            wspr::ArithScope worker_mode(arith);
             const int dev = k % count;
             if (hipSetDevice(dev) != hipSuccess) { rcs[k] = -1; return; }
             Context::bind_lane(lane0 + k / count);
@@ -683,7 +690,8 @@ int wspr_stage_fft_bank(const float* idat, const float* qdat, int nseg, int samp
         const int blocks = 4 * (samples / wspr::kFftSize) - 1;
         c.load_host(idat, qdat, nseg, samples, seg_stride);
         float* ps = c.ps_buffer(nseg);
-        wspr::launch_fft_bank(c.work_i(nseg), c.work_q(nseg), nullptr, nseg, samples, ps, c.tables(), c.stream());
+        wspr::launch_fft_bank(c.work_i(nseg), c.work_q(nseg), nullptr, nseg, samples, ps, c.tables(), c.stream(),
+                              wspr::call_arith());
         std::vector<float> h((size_t)nseg * wspr::kPsBins * wspr::kPsTPitch);
         HIP_TRY(hipMemcpyAsync(h.data(), ps, h.size() * 4, hipMemcpyDeviceToHost, c.stream()));
         c.sync();
@@ -868,6 +876,11 @@ int wspr_set_front_end_cus(int ncus) {
     return wspr::front_end_cus().exchange(ncus < 0 ? 0 : ncus);
 }
 #endif  // WSPR_LAB
+
+int wspr_set_arithmetic(int mode) {
+    if (mode != 0 && mode != 1) return -1;
+    return wspr::arith_setting().exchange(mode);
+}
 
 int wspr_set_fano_device_mode(int mode) {
     return wspr::fano_device_setting().exchange(mode < 0 ? -1 : (mode ? 1 : 0));
@@ -1120,6 +1133,7 @@ int wspr_session_decode(wspr_session* s, int buffer, struct decoder_results* dec
 int wspr_session_decode_many(wspr_session* const* sessions, const int* buffers, int n, struct decoder_results* decodes,
                              int max_results, int* n_results, int* decoded) {
     if (!sessions || !buffers || n < 0 || !decodes || max_results < 1 || !n_results) return -1;
+    wspr::ArithScope call_mode;            // one mode for every group of options this call decodes
     for (int k = 0; k < n; ++k) {
         n_results[k] = 0;
         if (decoded) decoded[k] = 0;

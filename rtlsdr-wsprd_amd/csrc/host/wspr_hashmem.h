@@ -44,6 +44,7 @@ struct HashBatch {
     // what a later WSPR_HASH_REVISIT must find unchanged: the call completed (valid), over this many slots and samples
     bool valid = false;
     int nslots = 0, samples = 0;
+    int arith = 0;                                  // wspr_set_arithmetic() mode of the call (a revisit must match it)
 
     HashBatch();
     void load_file();                               // hashtable.txt of the working directory (wsprd.c:481-494)

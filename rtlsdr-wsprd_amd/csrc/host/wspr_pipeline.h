@@ -28,6 +28,21 @@ std::atomic<int>& node_share();
 // CUs the front end (K0) may occupy, 0 = all (wspr_set_front_end_cus / WSPR_K0_CUS)
 std::atomic<int>& front_end_cus();
 
+// wspr_set_arithmetic(): the process-wide mode (0 exact, 1 contracted).  A call reads it ONCE, on entry (ArithScope in
+// the outermost entry point of the calling thread), and every launch of that call uses call_arith(); threads a call
+// starts for itself (slots, node workers) install the caller's value with ArithScope(mode).
+std::atomic<int>& arith_setting();
+int& call_arith_slot();                                   // thread-local: the current call's mode, -1 outside a call
+inline int call_arith() { const int m = call_arith_slot(); return m < 0 ? arith_setting().load() : m; }
+struct ArithScope {
+    bool owner;
+    ArithScope() : owner(call_arith_slot() < 0) { if (owner) call_arith_slot() = arith_setting().load(); }
+    explicit ArithScope(int mode) : owner(call_arith_slot() < 0) { if (owner) call_arith_slot() = mode; }
+    ~ArithScope() { if (owner) call_arith_slot() = -1; }
+    ArithScope(const ArithScope&) = delete;
+    ArithScope& operator=(const ArithScope&) = delete;
+};
+
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt
     std::vector<unsigned char> sym;       // 162 soft symbols each, transmission order

@@ -32,8 +32,8 @@ static void fft_and_average(const float* dI, const float* dQ, const int* d_segli
     static const int fused_cfg = [] { const char* e = lab_env("WSPR_K1_FUSED"); return e ? atoi(e) : -1; }();
     const bool fused = fused_cfg < 0 ? nactive >= 256 : fused_cfg != 0;
     mark();
-    if (fused) launch_fft_bank_avg(dI, dQ, d_seglist, nactive, samples, ps, psavg, tab, st);
-    else launch_fft_bank(dI, dQ, d_seglist, nactive, samples, ps, tab, st);
+    if (fused) launch_fft_bank_avg(dI, dQ, d_seglist, nactive, samples, ps, psavg, tab, st, call_arith());
+    else launch_fft_bank(dI, dQ, d_seglist, nactive, samples, ps, tab, st, call_arith());
     mark(); mark();
     if (!fused) launch_time_average(ps, d_seglist, nactive, blocks, psavg, st);
     mark();
@@ -196,6 +196,15 @@ std::atomic<int>& fano_device_setting() {
     return v;
 }
 static int fano_device_mode() { return fano_device_setting().load(); }
+
+std::atomic<int>& arith_setting() {
+    static std::atomic<int> v{0};
+    return v;
+}
+int& call_arith_slot() {
+    thread_local int m = -1;
+    return m;
+}
 
 std::atomic<unsigned>& fano_fast_budget() {
     static std::atomic<unsigned> v{[] { const char* e = getenv("WSPR_FANO_FAST"); return e ? (unsigned)atoi(e) : 10000u; }()};
@@ -528,9 +537,9 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
         upload(d_items, h_items, (size_t)nw * sizeof(FineState), c.stream);
         upload(d_lists, h_lists, (size_t)nw * 2 * 4, c.stream);
         // mode 0: lag scan (tiled), mode 1: 5 frequencies, mode 2: first rung of the ladder
-        launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream);
+        launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream, call_arith());
         launch_demod_tiled(wi, wq, samples, d_items, nw, d_lists, n_shared, d_lists + nw, n_own, 0, nlag0, lagstep,
-                           0.0f, d_tabs, d_pw, d_sync, nullptr, nullptr, c.tab, c.stream);
+                           0.0f, d_tabs, d_pw, d_sync, nullptr, nullptr, c.tab, c.stream, call_arith());
         launch_pick_lag(d_items, nw, d_sync, nlag0, lagstep, c.stream);
         std::vector<FineState> tr_items0;
         if (trace) {                                           // mode-0 result, before the frequency scan refines it
@@ -547,7 +556,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
             float* d_pwf = static_cast<float*>(c.pwfreq.need((size_t)nw * 5 * kNSymD * 16));
             launch_freq_scan_and_first_rung(wi, wq, samples, d_items, d_lists, n_shared, d_lists + nw, n_own, lagstep,
                                             minsync1, c.t_jitter.as<int>(), d_tabs1, d_pwf, d_scr, d_sync0, d_sym0,
-                                            d_rms0, c.tab, c.stream, d_pw, nlag0);
+                                            d_rms0, c.tab, c.stream, d_pw, nlag0, call_arith());
         }
         // device-Fano mode: the soft symbols stay in HBM, only items / sync / rms come down
         HIP_OK(hipMemcpyAsync(h_down, d_blk, (c.dev_fano && !trace) ? o_sym : down_bytes, hipMemcpyDeviceToHost, c.stream));
@@ -645,7 +654,7 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
             Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[3]);
             upload(d_items, h2, (size_t)na * sizeof(FineState), c.stream);
             upload(d_lists, h_lists, (size_t)na * 2 * 4, c.stream);
-            launch_phasor_tables(d_items, na, 2, d_tabs, c.stream);
+            launch_phasor_tables(d_items, na, 2, d_tabs, c.stream, call_arith());
             // the 43-lag outputs in one block [sync | rms | symbols] -> one copy down
             const size_t o_rms = (size_t)na * kMaxLags * 4, o_sym = 2 * o_rms, blk = o_sym + (size_t)na * kMaxLags * kNSymD;
             char* d_blk = static_cast<char*>(c.symbuf.need(blk));
@@ -654,7 +663,7 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
             d_rms = reinterpret_cast<float*>(d_blk + o_rms);
             d_sym = reinterpret_cast<unsigned char*>(d_blk + o_sym);
             launch_demod_tiled(wi, wq, samples, d_items, na, d_lists, n_shared, d_lists + na, n_own, 2, kMaxLags, 3,
-                               minsync1, d_tabs, d_pw, d_sync, d_sym, d_rms, c.tab, c.stream);
+                               minsync1, d_tabs, d_pw, d_sync, d_sym, d_rms, c.tab, c.stream, call_arith());
             HIP_OK(hipMemcpyAsync(h_blk, d_blk, c.dev_fano ? o_sym : blk, hipMemcpyDeviceToHost, c.stream));
             t.stop();
             c.resolve_deferred();
@@ -890,7 +899,7 @@ void Context::DecodeRun::subtract(const std::vector<SubJob>& jobs) {
     const int slot_ev = c.n_def < Impl::kDeferred ? c.n_def : -1;
     if (slot_ev >= 0) HIP_OK(hipEventRecord(c.ev_def[slot_ev][0], c.stream));
     upload(dj, hj, (size_t)nj * sizeof(SubJob), c.stream);
-    launch_subtract(c.iqI.as<float>(), c.iqQ.as<float>(), samples, dj, nj, scratch, c.tab, c.stream);
+    launch_subtract(c.iqI.as<float>(), c.iqQ.as<float>(), samples, dj, nj, scratch, c.tab, c.stream, call_arith());
     if (slot_ev >= 0) {
         HIP_OK(hipEventRecord(c.ev_def[slot_ev][1], c.stream));
         c.def_acc[slot_ev] = &c.t_ms[4];
@@ -1075,7 +1084,7 @@ int Context::bench_valu(int nseg, int samples, int iters, double* ms) {
     HIP_OK(hipMemcpyAsync(d_items, items.data(), (size_t)nw * sizeof(FineState), hipMemcpyHostToDevice, c.stream));
     HIP_OK(hipMemcpyAsync(d_lists, lists.data(), (size_t)nw * 2 * 4, hipMemcpyHostToDevice, c.stream));
     HIP_OK(hipMemcpyAsync(dj, jobs.data(), (size_t)nw * sizeof(SubJob), hipMemcpyHostToDevice, c.stream));
-    launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream);
+    launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream, call_arith());
     HIP_OK(hipStreamSynchronize(c.stream));
     hipEvent_t e[4];
     for (auto& x : e) HIP_OK(hipEventCreate(&x));
@@ -1084,14 +1093,14 @@ int Context::bench_valu(int nseg, int samples, int iters, double* ms) {
     for (int it = -1; it < iters; ++it) {                    // pass -1 is not timed (first touch of the buffers, clocks)
         HIP_OK(hipEventRecord(e[0], c.stream));
         launch_demod_tiled(wi, wq, samples, d_items, nw, d_lists, n_shared, d_lists + nw, n_own, 0, 33, 8, 0.0f, d_tabs,
-                           d_pw, d_sync, nullptr, nullptr, c.tab, c.stream);
+                           d_pw, d_sync, nullptr, nullptr, c.tab, c.stream, call_arith());
         HIP_OK(hipEventRecord(e[1], c.stream));
         launch_pick_lag(d_items, nw, d_sync, 33, 8, c.stream);
         launch_freq_scan_and_first_rung(wi, wq, samples, d_items, d_lists, n_shared, d_lists + nw, n_own, 8, 0.10f,
                                         c.t_jitter.as<int>(), d_tabs, d_pwf, d_scr, d_sync, d_sym, d_rms, c.tab, c.stream,
-                                        d_pw, 33);
+                                        d_pw, 33, call_arith());
         HIP_OK(hipEventRecord(e[2], c.stream));
-        launch_subtract(c.iqI.as<float>(), c.iqQ.as<float>(), samples, dj, nw, scratch, c.tab, c.stream);
+        launch_subtract(c.iqI.as<float>(), c.iqQ.as<float>(), samples, dj, nw, scratch, c.tab, c.stream, call_arith());
         HIP_OK(hipEventRecord(e[3], c.stream));
         HIP_OK(hipEventSynchronize(e[3]));
         float t = 0;
@@ -1102,7 +1111,7 @@ int Context::bench_valu(int nseg, int samples, int iters, double* ms) {
         }
         // the frequency scan refined the items: restore the coarse state for the next round
         HIP_OK(hipMemcpyAsync(d_items, items.data(), (size_t)nw * sizeof(FineState), hipMemcpyHostToDevice, c.stream));
-        launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream);
+        launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream, call_arith());
         HIP_OK(hipStreamSynchronize(c.stream));
     }
     for (auto& x : e) (void)hipEventDestroy(x);

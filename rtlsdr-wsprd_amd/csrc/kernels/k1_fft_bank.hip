@@ -151,7 +151,11 @@ static_assert(out_rows_share_a_skew(), "every kOutRow[r] is 16 mod 64: one skew 
 // One FFT of the run: window, 3 passes, power into the workgroup's output tile.  `raw` is the sliding
 // window of raw samples, raw[(base + r) & 7] = row r of this block; rotating `base` by 2 per block
 // instead of moving registers needs the run loop unrolled by 4 (kBase is a compile-time constant).
-template <int kBase, int kPitch, bool kBarrierBeforeWrite = false, bool kRefill = false>
+// The powers of wsprd.c:551, re*re + im*im: kFma (wspr_set_arithmetic, contracted mode) fuses them as clang's
+// -ffp-contract=on does, fma(re, re, im*im); otherwise two separately rounded products and their sum.
+__device__ __forceinline__ float power_fma(const v2 x) { return __builtin_fmaf(x.x, x.x, x.y * x.y); }
+
+template <bool kFma, int kBase, int kPitch, bool kBarrierBeforeWrite = false, bool kRefill = false>
 __device__ __forceinline__ void one_fft(v2 (&raw)[8], const float (&win)[8], const Tw& twA, const Tw& twB, float w8,
                                         v2* __restrict__ X, int lane, int a, int c,
                                         const float* __restrict__ si, const float* __restrict__ sq, int t, bool more,
@@ -200,7 +204,7 @@ __device__ __forceinline__ void one_fft(v2 (&raw)[8], const float (&win)[8], con
     for (int r = 0; r < 8; ++r) e[r] = x[r] * x[r];
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
-        const float pw = e[r].x + e[r].y;
+        const float pw = kFma ? power_fma(x[r]) : e[r].x + e[r].y;
         if (r == 1)      ob[ocol.at1] = pw;
         else if (r == 6) ob[ocol.at6] = pw;
         else ob[ocol.base + kOutRow[r] * kPitch] = pw;
@@ -221,7 +225,7 @@ __device__ __forceinline__ OutCols out_columns(int lane) {
                    lo < 17 ? (lo + kOutRow[6]) * kPitch + sk : spill};
 }
 
-template <int kRun>
+template <int kRun, bool kFma>
 __global__ __launch_bounds__(256)
 void fft_bank_kernel(const float* __restrict__ dI, const float* __restrict__ dQ,
                      const int* __restrict__ seg_list, int blocks, float* __restrict__ ps,
@@ -266,13 +270,13 @@ void fft_bank_kernel(const float* __restrict__ dI, const float* __restrict__ dQ,
             raw[r] = v2{si[k], sq[k]};
         }
         for (int t = t_begin; t < t_end; t += 4) {
-            one_fft<0, kOutPitch>(raw, win, twA, twB, w8, X, lane, a, c, si, sq, t, t + 1 < t_end, otile, ocol, t - t0);
+            one_fft<kFma, 0, kOutPitch>(raw, win, twA, twB, w8, X, lane, a, c, si, sq, t, t + 1 < t_end, otile, ocol, t - t0);
             if (t + 1 >= t_end) break;
-            one_fft<2, kOutPitch>(raw, win, twA, twB, w8, X, lane, a, c, si, sq, t + 1, t + 2 < t_end, otile, ocol, t + 1 - t0);
+            one_fft<kFma, 2, kOutPitch>(raw, win, twA, twB, w8, X, lane, a, c, si, sq, t + 1, t + 2 < t_end, otile, ocol, t + 1 - t0);
             if (t + 2 >= t_end) break;
-            one_fft<4, kOutPitch>(raw, win, twA, twB, w8, X, lane, a, c, si, sq, t + 2, t + 3 < t_end, otile, ocol, t + 2 - t0);
+            one_fft<kFma, 4, kOutPitch>(raw, win, twA, twB, w8, X, lane, a, c, si, sq, t + 2, t + 3 < t_end, otile, ocol, t + 2 - t0);
             if (t + 3 >= t_end) break;
-            one_fft<6, kOutPitch>(raw, win, twA, twB, w8, X, lane, a, c, si, sq, t + 3, t + 4 < t_end, otile, ocol, t + 3 - t0);
+            one_fft<kFma, 6, kOutPitch>(raw, win, twA, twB, w8, X, lane, a, c, si, sq, t + 3, t + 4 < t_end, otile, ocol, t + 3 - t0);
         }
     }
     __syncthreads();
@@ -305,7 +309,7 @@ void fft_bank_kernel(const float* __restrict__ dI, const float* __restrict__ dQ,
 // the group's first block, rows 10..13 replace rows 0..3 once the first pair has been windowed (kFirst = 0), and
 // the next group's rows 0..9 are fetched once the second pair has (kFirst = 4).  obA/obB: the tile columns of the two
 // powers; where the second FFT does not exist (the segment's last blocks) it runs on clamped rows and writes nothing.
-template <int kFirst, int kPitch, bool kBarrierBeforeWrite>
+template <bool kFma, int kFirst, int kPitch, bool kBarrierBeforeWrite>
 __device__ __forceinline__ void fft_pair(v2 (&S)[10], const float (&win)[8], const Tw& twA, const Tw& twB, float w8,
                                          v2* __restrict__ X, int lane, int a, int c,
                                          const float* __restrict__ si, const float* __restrict__ sq, int k_next,
@@ -368,7 +372,7 @@ __device__ __forceinline__ void fft_pair(v2 (&S)[10], const float (&win)[8], con
         for (int r = 0; r < 8; ++r) e[r] = xa[r] * xa[r];
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const float pw = e[r].x + e[r].y;
+            const float pw = kFma ? power_fma(xa[r]) : e[r].x + e[r].y;
             if (r == 1)      obA[ocol.at1] = pw;
             else if (r == 6) obA[ocol.at6] = pw;
             else obA[ocol.base + kOutRow[r] * kPitch] = pw;
@@ -382,7 +386,7 @@ __device__ __forceinline__ void fft_pair(v2 (&S)[10], const float (&win)[8], con
         for (int r = 0; r < 8; ++r) e[r] = xb[r] * xb[r];
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
-            const float pw = e[r].x + e[r].y;
+            const float pw = kFma ? power_fma(xb[r]) : e[r].x + e[r].y;
             if (r == 1)      obB[ocol.at1] = pw;
             else if (r == 6) obB[ocol.at6] = pw;
             else obB[ocol.base + kOutRow[r] * kPitch] = pw;
@@ -396,7 +400,7 @@ __device__ __forceinline__ void fft_pair(v2 (&S)[10], const float (&win)[8], con
 // running sum is the reference's serial one.  The spectrogram is then never read back for the average:
 // the stage's HBM traffic drops from IQ + 2 x ps to IQ + ps.  A wave's four blocks are consecutive (sliding
 // sample window inside the group); between groups the window is reloaded (the rows come from the caches).
-template <int kRun>
+template <int kRun, bool kFma>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void fft_bank_avg_kernel(const float* __restrict__ dI, const float* __restrict__ dQ,
                          const int* __restrict__ seg_list, int blocks, float* __restrict__ ps,
@@ -451,10 +455,10 @@ void fft_bank_avg_kernel(const float* __restrict__ dI, const float* __restrict__
             float* const ob = otile + (t_begin - t0);
             // the barrier that frees the tile sits inside the first pair, just before its first powers are written:
             // a wave that is done with the previous tile starts computing at once
-            fft_pair<0, kOutPitch, true>(S, win, twA, twB, w8, X, lane, a, c, si, sq, kHop * t_begin + 640,
+            fft_pair<kFma, 0, kOutPitch, true>(S, win, twA, twB, w8, X, lane, a, c, si, sq, kHop * t_begin + 640,
                                          ob, ob + 1, n_here >= 2, ocol);
             if (n_here >= 3)        // (a group with fewer blocks for this wave is the segment's last: nothing to refill)
-                fft_pair<4, kOutPitch, false>(S, win, twA, twB, w8, X, lane, a, c, si, sq, kHop * (t_begin + kWgTimes),
+                fft_pair<kFma, 4, kOutPitch, false>(S, win, twA, twB, w8, X, lane, a, c, si, sq, kHop * (t_begin + kWgTimes),
                                               ob + 2, ob + 3, n_here >= 4, ocol);
         } else {
             __syncthreads();
@@ -585,7 +589,7 @@ void launch_calib_copy16(const float* src, float* dst, size_t n, hipStream_t st,
 #endif  // WSPR_LAB
 
 void launch_fft_bank(const float* dI, const float* dQ, const int* seg_list, int nseg_active,
-                     int samples, float* ps, const DeviceTables& t, hipStream_t st) {
+                     int samples, float* ps, const DeviceTables& t, hipStream_t st, int arith) {
     const int blocks = 4 * (samples / kFftSize) - 1;
     if (blocks <= 0 || nseg_active <= 0) return;
     // four consecutive FFTs per wave: a workgroup covers 16 time blocks (64-byte row segments, 47 KB of LDS, three
@@ -594,21 +598,23 @@ void launch_fft_bank(const float* dI, const float* dQ, const int* seg_list, int 
     constexpr int R = 4;
     constexpr int per_wg = R * kWavesPerWg;
     const size_t lds = kWavesPerWg * kTile * sizeof(v2) + ((size_t)kPsBins * (per_wg + 1) + kOutSpill) * sizeof(float);
-    static std::atomic<unsigned> opted{0};
-    lds_opt_in(reinterpret_cast<const void*>(&fft_bank_kernel<R>), lds, opted);
+    static std::atomic<unsigned> opted{0}, opted_fma{0};
+    auto kernel = arith ? fft_bank_kernel<R, true> : fft_bank_kernel<R, false>;
+    lds_opt_in(reinterpret_cast<const void*>(kernel), lds, arith ? opted_fma : opted);
     dim3 grid((blocks + per_wg - 1) / per_wg, nseg_active);
-    hipLaunchKernelGGL(fft_bank_kernel<R>, grid, dim3(256), lds, st, dI, dQ, seg_list, blocks, ps, t.window, t.twiddle);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, dI, dQ, seg_list, blocks, ps, t.window, t.twiddle);
 }
 
 // K1 + K2a in one kernel (see fft_bank_avg_kernel); one workgroup per segment, so only for batches that
 // fill the GPU on their own.
 void launch_fft_bank_avg(const float* dI, const float* dQ, const int* seg_list, int nseg_active,
-                         int samples, float* ps, float* psavg, const DeviceTables& t, hipStream_t st) {
+                         int samples, float* ps, float* psavg, const DeviceTables& t, hipStream_t st, int arith) {
     const int blocks = 4 * (samples / kFftSize) - 1;
     if (blocks <= 0 || nseg_active <= 0) return;
     constexpr int R = 4;
     const size_t lds = kWavesPerWg * kTile * sizeof(v2) + ((size_t)kPsBins * (R * kWavesPerWg + 1) + kOutSpill) * sizeof(float);
-    hipLaunchKernelGGL(fft_bank_avg_kernel<R>, dim3(nseg_active), dim3(256), lds, st, dI, dQ, seg_list, blocks, ps,
+    auto kernel = arith ? fft_bank_avg_kernel<R, true> : fft_bank_avg_kernel<R, false>;
+    hipLaunchKernelGGL(kernel, dim3(nseg_active), dim3(256), lds, st, dI, dQ, seg_list, blocks, ps,
                        psavg, t.window, t.twiddle);
 }
 

@@ -34,11 +34,19 @@ constexpr double kTwoPiDt = 2.0 * 3.14159265358979323846 * 1.0 / 375.0;   // TWO
 constexpr double kDf05 = 375.0 / 256.0 * 0.5;
 constexpr double kDf15 = 375.0 / 256.0 * 1.5;
 
+// Arithmetic policy (wspr_set_arithmetic): every kernel that evaluates a contraction site of wsprd.c is a template on
+// kFma.  kFma = false is the exact mode: separately rounded multiplies and adds, the source as it always was.
+// kFma = true is the contracted mode: each site as clang's -ffp-contract=on fuses it in wsprd.c, the LEFT product of a
+// sum into the fma (a*b + c*d -> fma(a, b, c*d), (acc + x*c) + y*s -> fma(y, s, fma(x, c, acc)), acc - x*s ->
+// fma(-x, s, acc)); per-lane accumulation order stays the reference's loop order.
+__device__ __forceinline__ float fmaf1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+
 constexpr int kGenThreads = 192;
 constexpr int kGenChunk = 32;
 constexpr int kGenPerThread = kNSymD * kGenChunk / kGenThreads;     // 27 samples staged per thread and chunk
 static_assert(kNSymD * kGenChunk % kGenThreads == 0, "chunk must split evenly over the workgroup");
 
+template <bool kFma>
 __global__ __launch_bounds__(kGenThreads)
 void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
                   const FineState* __restrict__ items, const int* __restrict__ item_list, int mode,
@@ -56,7 +64,8 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
         f0 = st.freq_coarse;
         lag = st.shift_coarse - 128 + lagstep * hyp;
     } else if (mode == 1) {
-        f0 = st.freq + (float)(ifmin + hyp) * fstep;      // *freq + ifreq * fstep, wsprd.c:151
+        if constexpr (kFma) f0 = fmaf1((float)(ifmin + hyp), fstep, st.freq);
+        else f0 = st.freq + (float)(ifmin + hyp) * fstep;      // *freq + ifreq * fstep, wsprd.c:151
         lag = st.shift;
     } else {
         if (!(st.sync > minsync1)) return;              // not worth a try (wsprd.c:733-737)
@@ -112,20 +121,31 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
                 if (kGenChunk * ch + jj > 0) {
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
+                        if constexpr (kFma) {
+                            const float cn = fmaf1(c[t], cd[t], -(s[t] * sd[t]));
+                            s[t] = fmaf1(c[t], sd[t], s[t] * cd[t]);
+                            c[t] = cn;
+                        } else {
                         const float a = c[t] * cd[t], b = s[t] * sd[t];
                         const float e = c[t] * sd[t], d = s[t] * cd[t];
                         c[t] = a - b;
                         s[t] = e + d;
+                        }
                     }
                 }
                 if (k > 0 && k < np) {
                     const float2 xy = tile[i][jj];
 #pragma unroll
                     for (int t = 0; t < 4; ++t) {
+                        if constexpr (kFma) {
+                            ai[t] = fmaf1(xy.y, s[t], fmaf1(xy.x, c[t], ai[t]));
+                            aq[t] = fmaf1(xy.y, c[t], fmaf1(-xy.x, s[t], aq[t]));
+                        } else {
                         const float m1 = xy.x * c[t], m2 = xy.y * s[t];
                         const float m3 = xy.x * s[t], m4 = xy.y * c[t];
                         ai[t] = (ai[t] + m1) + m2;
                         aq[t] = (aq[t] - m3) + m4;
+                        }
                     }
                 }
             }
@@ -134,8 +154,12 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
     if (i < kNSymD) {
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
+            if constexpr (kFma) {
+                pw[i][t] = sqrtf(fmaf1(ai[t], ai[t], aq[t] * aq[t]));
+            } else {
             const float e1 = ai[t] * ai[t], e2 = aq[t] * aq[t];
             pw[i][t] = sqrtf(e1 + e2);
+            }
         }
     }
     __syncthreads();
@@ -162,8 +186,13 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
                 const float ff = f * f;
                 f2sum += ff / 162.0f;
             }
+            float fac;
+            if constexpr (kFma) {
+                fac = sqrtf(fmaf1(-fsum, fsum, f2sum));
+            } else {
             const float m2 = fsum * fsum;
-            const float fac = sqrtf(f2sum - m2);
+            fac = sqrtf(f2sum - m2);
+            }
             float sq = 0.0f;
             unsigned char* __restrict__ so = sym_out + o * kNSymD;
             for (int k = 0; k < kNSymD; ++k) {
@@ -202,23 +231,60 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
 // sequence -- and therefore every bit -- is unchanged.  Tones (0,1) and (2,3) share a pair.
 typedef float v2f __attribute__((ext_vector_type(2)));
 
+// Contracted mode (kFma): each site is one v_pk_fma_f32 on the pair, i.e. two IEEE fmas (wsprd.c:200-207 fuse as
+// fma(y, s, fma(x, c, ai)) and fma(y, c, fma(-x, s, aq)), wsprd.c:211-214 as fma(i, i, q*q)).
+__device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
+
+template <bool kFma>
 struct ToneAcc {
     v2f i01, i23, q01, q23;
     __device__ __forceinline__ void clear() { i01 = i23 = q01 = q23 = (v2f){0.0f, 0.0f}; }
+    // contracted mode: one sample (x, y) on the four tones' pairs (c01, c23, s01, s23)
+    __device__ __forceinline__ void step_fma(const v2f xx, const v2f yy, const v2f c01, const v2f c23, const v2f s01,
+                                             const v2f s23) {
+        const v2f nx = -xx;
+        i01 = fma2(yy, s01, fma2(xx, c01, i01));
+        i23 = fma2(yy, s23, fma2(xx, c23, i23));
+        q01 = fma2(yy, c01, fma2(nx, s01, q01));
+        q23 = fma2(yy, c23, fma2(nx, s23, q23));
+    }
     // ai = (ai + x*c) + y*s ; aq = (aq - x*s) + y*c   (wsprd.c:200-207)
     __device__ __forceinline__ void step(const float2 d, const float4 c4, const float4 s4) {
         const v2f xx = {d.x, d.x}, yy = {d.y, d.y};
         const v2f c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w}, s01 = {s4.x, s4.y}, s23 = {s4.z, s4.w};
+        if constexpr (kFma) {
+            step_fma(xx, yy, c01, c23, s01, s23);
+        } else {
         i01 = (i01 + xx * c01) + yy * s01;
         i23 = (i23 + xx * c23) + yy * s23;
         q01 = (q01 - xx * s01) + yy * c01;
         q23 = (q23 - xx * s23) + yy * c23;
+        }
     }
     __device__ __forceinline__ float4 amplitudes() const {
+        if constexpr (kFma) {
+            const v2f e01 = fma2(i01, i01, q01 * q01), e23 = fma2(i23, i23, q23 * q23);
+            return make_float4(sqrtf(e01.x), sqrtf(e01.y), sqrtf(e23.x), sqrtf(e23.y));
+        } else {
         const v2f e01 = i01 * i01 + q01 * q01, e23 = i23 * i23 + q23 * q23;
         return make_float4(sqrtf(e01.x), sqrtf(e01.y), sqrtf(e23.x), sqrtf(e23.y));
+        }
     }
 };
+
+// One step of the phasor recurrence (wsprd.c:180-187): c' = c*cd - s*sd, s' = c*sd + s*cd
+template <bool kFma>
+__device__ __forceinline__ void phasor_step(float& c, float& s, float cd, float sd) {
+    if constexpr (kFma) {
+        const float cn = fmaf1(c, cd, -(s * sd));
+        s = fmaf1(c, sd, s * cd);
+        c = cn;
+    } else {
+        const float a = c * cd, b = s * sd, e = c * sd, d = s * cd;
+        c = a - b;
+        s = e + d;
+    }
+}
 
 constexpr int kTileSymsShared = 9;    // 9 x 33 lags = 297 of 320 lanes; 28 KB of LDS
 constexpr int kTileSymsOwn = 6;       // per-symbol tables: 6 x 8 KB + tile
@@ -227,6 +293,7 @@ constexpr int kTileSymsOwn = 6;       // per-symbol tables: 6 x 8 KB + tile
 // the LDS cycles of the kernel).  Two extra 16-byte words per table move consecutive symbols 8 banks apart.
 constexpr int kOwnTabPitch = 512 + 2;           // float4 words per table in LDS
 
+template <bool kFma>
 __global__ __launch_bounds__(64)
 void phasor_table_kernel(const FineState* __restrict__ items, int mode, float* __restrict__ tabs) {
     const int item = blockIdx.y;
@@ -243,17 +310,13 @@ void phasor_table_kernel(const FineState* __restrict__ items, int mode, float* _
     float* __restrict__ t = tabs + (size_t)st.pad * 2048;   // [256][8]
     float c = 1.0f, s = 0.0f;
     for (int j = 0; j < kSps; ++j) {
-        if (j > 0) {
-            const float a = c * cd, b = s * sd, e = c * sd, d = s * cd;
-            c = a - b;
-            s = e + d;
-        }
+        if (j > 0) phasor_step<kFma>(c, s, cd, sd);
         t[8 * j + tone] = c;
         t[8 * j + 4 + tone] = s;
     }
 }
 
-template <int STEP, bool SHARED>
+template <int STEP, bool SHARED, bool kFma>
 __global__ __launch_bounds__(448)
 void demod_tile_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
                        const FineState* __restrict__ items, const int* __restrict__ item_list, int mode,
@@ -293,11 +356,7 @@ void demod_tile_kernel(const float* __restrict__ dI, const float* __restrict__ d
             float* __restrict__ t = reinterpret_cast<float*>(tab + il * kOwnTabPitch);     // [256][8]
             float c = 1.0f, s = 0.0f;
             for (int j = 0; j < kSps; ++j) {
-                if (j > 0) {
-                    const float a = c * cd, b = s * sd, e = c * sd, d = s * cd;
-                    c = a - b;
-                    s = e + d;
-                }
+                if (j > 0) phasor_step<kFma>(c, s, cd, sd);
                 t[8 * j + tone] = c;
                 t[8 * j + 4 + tone] = s;
             }
@@ -322,7 +381,7 @@ void demod_tile_kernel(const float* __restrict__ dI, const float* __restrict__ d
     const int il = tid / nlag, m = tid - il * nlag;
     if (il >= kTileSyms) return;
     const float4* __restrict__ tb = tab + (SHARED ? 0 : il * kOwnTabPitch);
-    ToneAcc acc;
+    ToneAcc<kFma> acc;
     acc.clear();
     if constexpr (STEP == 8 || STEP == 16) {
         // e = STEP*m + 256*il + j with STEP | 256: row = j % STEP, column = m + (256/STEP)*il + j/STEP
@@ -386,6 +445,7 @@ constexpr int kDrTabStride = 2 * kDrChunk + 2;      // float4 words per symbol i
 
 __device__ __forceinline__ int drift_tile_word(int e) { return (e & 7) * kDrPitch + (e >> 3) + kDrSkew * (e >> 8); }
 
+template <bool kFma>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 3)))
 void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
                         const FineState* __restrict__ items, const int* __restrict__ item_list,
@@ -429,7 +489,7 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
     const bool working = (lane < kDrSyms * kDrGroups) && (i0 + il < kNSymD);
     const float4* __restrict__ tb = tab + (working ? il : 0) * kDrTabStride;
     const int e_lane = 8 * g + kSps * (working ? il : 0);
-    ToneAcc acc[3];
+    ToneAcc<kFma> acc[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) acc[r].clear();
     for (int ch = 0; ch < kSps / kDrChunk; ++ch) {
@@ -437,9 +497,13 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
         if (builder) {
             for (int jj = 0; jj < kDrChunk; ++jj) {
                 if (ch + jj > 0) {
+                    if constexpr (kFma) {
+                        phasor_step<true>(pc, ps, cd, sd);
+                    } else {
                     const float a = pc * cd, b = ps * sd, e = pc * sd, d = ps * cd;
                     pc = a - b;
                     ps = e + d;
+                    }
                 }
                 tabw[8 * jj] = pc;
                 tabw[8 * jj + 4] = ps;
@@ -472,6 +536,11 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
                         for (int r = 0; r < 3; ++r) dn[r] = t0[r][(u + 1) * kDrPitch];
                     }
                     const v2f c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w}, s01 = {s4.x, s4.y}, s23 = {s4.z, s4.w};
+                    if constexpr (kFma) {
+#pragma unroll
+                        for (int r = 0; r < 3; ++r)
+                            acc[r].step_fma((v2f){d[r].x, d[r].x}, (v2f){d[r].y, d[r].y}, c01, c23, s01, s23);
+                    } else {
                     v2f p[3][8];
 #pragma unroll
                     for (int r = 0; r < 3; ++r) {
@@ -488,6 +557,7 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
                     for (int r = 0; r < 3; ++r) {
                         acc[r].i01 = acc[r].i01 + p[r][4]; acc[r].i23 = acc[r].i23 + p[r][5];
                         acc[r].q01 = acc[r].q01 + p[r][6]; acc[r].q23 = acc[r].q23 + p[r][7];
+                    }
                     }
                     c4 = cn; s4 = sn;
 #pragma unroll
@@ -545,8 +615,9 @@ __device__ __forceinline__ float wave_shl1(float old, float src) {
 }
 
 // the whole wave lies inside the record: no bounds tests anywhere
+template <bool kFma>
 __device__ __forceinline__ void lagsys_wave(const float* __restrict__ xi, const float* __restrict__ xq, int kw,
-                                            const float4* __restrict__ gtab, ToneAcc (&acc)[kSysRows]) {
+                                            const float4* __restrict__ gtab, ToneAcc<kFma> (&acc)[kSysRows]) {
     constexpr int R = kSysRows, NS = R + 1;
     const int lane = threadIdx.x;
     // slot = one 8-sample vector: [0..3] pairs of I, [4..7] pairs of Q
@@ -608,12 +679,16 @@ __device__ __forceinline__ void lagsys_wave(const float* __restrict__ xi, const 
                         const v2f iv = S[(bb + r) % NS][q], qv = S[(bb + r) % NS][4 + q];
                         const float x = u ? iv.y : iv.x, y = u ? qv.y : qv.x;
                         const v2f xx = {x, x}, yy = {y, y};
+                        if constexpr (kFma) {
+                            acc[r].step_fma(xx, yy, c01, c23, s01, s23);
+                        } else {
                         const v2f p0 = xx * c01, p1 = xx * c23, p2 = xx * s01, p3 = xx * s23;
                         const v2f p4 = yy * s01, p5 = yy * s23, p6 = yy * c01, p7 = yy * c23;
                         acc[r].i01 = acc[r].i01 + p0; acc[r].i23 = acc[r].i23 + p1;
                         acc[r].q01 = acc[r].q01 - p2; acc[r].q23 = acc[r].q23 - p3;
                         acc[r].i01 = acc[r].i01 + p4; acc[r].i23 = acc[r].i23 + p5;
                         acc[r].q01 = acc[r].q01 + p6; acc[r].q23 = acc[r].q23 + p7;
+                        }
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -632,7 +707,8 @@ __device__ __forceinline__ void lagsys_wave(const float* __restrict__ xi, const 
     }
 }
 
-__device__ __forceinline__ void lagsys_store(const ToneAcc (&acc)[kSysRows], int u0, size_t item, float4* __restrict__ pw_out) {
+template <bool kFma>
+__device__ __forceinline__ void lagsys_store(const ToneAcc<kFma> (&acc)[kSysRows], int u0, size_t item, float4* __restrict__ pw_out) {
     constexpr int nlag = 33;
 #pragma unroll
     for (int r = 0; r < kSysRows; ++r) {
@@ -645,10 +721,11 @@ __device__ __forceinline__ void lagsys_store(const ToneAcc (&acc)[kSysRows], int
 
 // a wave that hangs over either end of the record (the first wave of an early candidate): every lane walks its
 // outputs sample by sample with the reference's bounds test
+template <bool kFma>
 __device__ __noinline__ void lagsys_edge_wave(const float* __restrict__ xi, const float* __restrict__ xq, int np, int kw,
                                               const float4* __restrict__ gtab, int u0, size_t item,
                                               float4* __restrict__ pw_out) {
-    ToneAcc acc[kSysRows];
+    ToneAcc<kFma> acc[kSysRows];
 #pragma unroll
     for (int r = 0; r < kSysRows; ++r) acc[r].clear();
     const int kl = kw + 8 * kSysRows * (int)threadIdx.x;
@@ -665,6 +742,7 @@ __device__ __noinline__ void lagsys_edge_wave(const float* __restrict__ xi, cons
 }
 
 // 154 VGPRs, three waves per SIMD (a 128-register build spills 28 dwords into the hot loop and runs 12 % slower)
+template <bool kFma>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void demod_lagsys_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
                          const FineState* __restrict__ items, const int* __restrict__ item_list, int nitems,
@@ -685,7 +763,7 @@ void demod_lagsys_kernel(const float* __restrict__ dI, const float* __restrict__
         const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
         const float4* __restrict__ tb = reinterpret_cast<const float4*>(tabs) + (size_t)st.pad * 512;
         const int k0 = st.shift_coarse - 128 + 8 * kSysOutputs;
-        ToneAcc a;
+        ToneAcc<kFma> a;
         a.clear();
 #pragma unroll 2
         for (int j = 0; j < kSps; ++j)
@@ -710,17 +788,18 @@ void demod_lagsys_kernel(const float* __restrict__ dI, const float* __restrict__
                                       (size_t)__builtin_amdgcn_readfirstlane(st.pad) * 512;
     // samples the wave touches: kw .. kw + 8 * 192 + 8 * 31 + 7 (one more vector is fetched and never used)
     if (kw > 0 && kw + 8 * kSysU + kSps + 8 <= np) {
-        ToneAcc acc[kSysRows];
+        ToneAcc<kFma> acc[kSysRows];
 #pragma unroll
         for (int r = 0; r < kSysRows; ++r) acc[r].clear();
-        lagsys_wave(xi, xq, kw, gtab, acc);
+        lagsys_wave<kFma>(xi, xq, kw, gtab, acc);
         lagsys_store(acc, u0, (size_t)item, pw_out);
     } else {
-        lagsys_edge_wave(xi, xq, np, kw, gtab, u0, (size_t)item, pw_out);
+        lagsys_edge_wave<kFma>(xi, xq, np, kw, gtab, u0, (size_t)item, pw_out);
     }
 }
 
 // folds the 162 per-symbol tone amplitudes of one (candidate, lag) in symbol order
+template <bool kFma>
 __global__ __launch_bounds__(64)
 void demod_metric_kernel(const float4* __restrict__ pw, const FineState* __restrict__ items, int nitems,
                          int mode, int nlag, float minsync1, float* __restrict__ sync_out,
@@ -749,8 +828,13 @@ void demod_metric_kernel(const float4* __restrict__ pw, const FineState* __restr
         const float ff = f * f;
         f2sum += ff / 162.0f;
     }
+    float fac;
+    if constexpr (kFma) {
+        fac = sqrtf(fmaf1(-fsum, fsum, f2sum));
+    } else {
     const float m2 = fsum * fsum;
-    const float fac = sqrtf(f2sum - m2);
+    fac = sqrtf(f2sum - m2);
+    }
     float sq = 0.0f;
     unsigned char* __restrict__ so = sym_out + (size_t)idx * kNSymD;
     for (int k = 0; k < kNSymD; ++k) {
@@ -789,6 +873,7 @@ __device__ __forceinline__ int centre_from_lag_scan(const FineState& st, int nla
     return m < nlag ? m : -1;
 }
 
+template <bool kFma>
 __global__ __launch_bounds__(64)
 void phasor_freq_kernel(const FineState* __restrict__ items, const int* __restrict__ item_list, int ifmin,
                         float fstep, float* __restrict__ tabs) {
@@ -796,7 +881,7 @@ void phasor_freq_kernel(const FineState* __restrict__ items, const int* __restri
     if (lane >= 4 * kNFreq) return;
     const FineState st = items[item_list[slot]];
     const int f = lane >> 2, tone = lane & 3;
-    const float f0 = st.freq + (float)(ifmin + f) * fstep;
+    const float f0 = kFma ? fmaf1((float)(ifmin + f), fstep, st.freq) : st.freq + (float)(ifmin + f) * fstep;
     const float fp = (float)((double)f0 + ((double)st.drift / 2.0) * (double)(0.0f - 81.0f) / (double)81.0f);
     const double off = (tone == 0) ? -kDf15 : (tone == 1) ? -kDf05 : (tone == 2) ? kDf05 : kDf15;
     const float dphi = (float)(kTwoPiDt * ((double)fp + off));
@@ -804,11 +889,7 @@ void phasor_freq_kernel(const FineState* __restrict__ items, const int* __restri
     float* __restrict__ t = tabs + ((size_t)slot * kNFreq + f) * 2048;
     float c = 1.0f, s = 0.0f;
     for (int j = 0; j < kSps; ++j) {
-        if (j > 0) {
-            const float a = c * cd, b = s * sd, e = c * sd, d = s * cd;
-            c = a - b;
-            s = e + d;
-        }
+        if (j > 0) phasor_step<kFma>(c, s, cd, sd);
         t[8 * j + tone] = c;
         t[8 * j + 4 + tone] = s;
     }
@@ -828,6 +909,7 @@ constexpr int kFsPerThread = (kNSymD * kFsChunk + kFsThreads - 1) / kFsThreads; 
 constexpr int kFqThreads = 768;                                   // 4 hypotheses x 3 waves
 constexpr int kFqPerThread = (kNSymD * kFsChunk + kFqThreads - 1) / kFqThreads;      // 7 samples staged per thread and chunk
 
+template <bool kFma>
 __global__ __launch_bounds__(kFqThreads) __attribute__((amdgpu_waves_per_eu(6, 8), amdgpu_num_vgpr(64)))
 void freq_scalar_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
                         const FineState* __restrict__ items, const int* __restrict__ item_list,
@@ -857,7 +939,7 @@ void freq_scalar_kernel(const float* __restrict__ dI, const float* __restrict__ 
         }
     };
     fetch(0);
-    ToneAcc acc;
+    ToneAcc<kFma> acc;
     acc.clear();
     for (int c = 0; c < kSps / kFsChunk; ++c) {
         __syncthreads();                                             // the previous chunk has been consumed
@@ -904,6 +986,7 @@ void freq_scalar_kernel(const float* __restrict__ dI, const float* __restrict__ 
 // The centre hypothesis of the candidates freq_scalar_kernel could not copy it for (rare: no lag won; or nlag = 0,
 // the WSPR_K4_FREQ=nocentre switch of the trace tests): one wave per candidate checks, and sums the 162 symbols
 // itself, three rounds of 64, samples straight from memory -- the same operations in the same order.
+template <bool kFma>
 __global__ __launch_bounds__(64)
 void freq_centre_rare_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
                              const FineState* __restrict__ items, const int* __restrict__ item_list,
@@ -915,7 +998,7 @@ void freq_centre_rare_kernel(const float* __restrict__ dI, const float* __restri
     const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
     const float4* __restrict__ gt = reinterpret_cast<const float4*>(tabs) + ((size_t)slot * kNFreq + kNFreq / 2) * (2 * kSps);
     for (int sym = threadIdx.x; sym < kNSymD; sym += 64) {
-        ToneAcc acc;
+        ToneAcc<kFma> acc;
         acc.clear();
         for (int j = 0; j < kSps; ++j) {
             const int k = st.shift + kSps * sym + j;
@@ -932,6 +1015,7 @@ void freq_centre_rare_kernel(const float* __restrict__ dI, const float* __restri
 // Staging, thread mapping and output layout are those of freq_tile_kernel, so freq_metric_kernel picks the
 // winner and forms the first rung's soft symbols for drifting candidates too (the general kernel ran the five
 // hypotheses as five workgroups and the first rung as a sixth pass over the samples).
+template <bool kFma>
 __global__ __launch_bounds__(kFsThreads) __attribute__((amdgpu_waves_per_eu(7, 8)))     // <= 72 VGPRs: two workgroups per CU
 void freq_drift_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
                        const FineState* __restrict__ items, const int* __restrict__ item_list, int ifmin, float fstep,
@@ -960,7 +1044,8 @@ void freq_drift_kernel(const float* __restrict__ dI, const float* __restrict__ d
     fetch(0);
     v2f cd01 = {1.0f, 1.0f}, cd23 = cd01, sd01 = {0.0f, 0.0f}, sd23 = sd01;
     if (working) {
-        const float f0 = st.freq + (float)(ifmin + f) * fstep;          // *freq + ifreq * fstep, wsprd.c:151
+        const float f0 = kFma ? fmaf1((float)(ifmin + f), fstep, st.freq)
+                              : st.freq + (float)(ifmin + f) * fstep;          // *freq + ifreq * fstep, wsprd.c:151
         const float fp = (float)((double)f0 + ((double)st.drift / 2.0) * (double)((float)sym - 81.0f) / (double)81.0f);
         const double fpd = (double)fp;
         float sn, cs;
@@ -970,7 +1055,7 @@ void freq_drift_kernel(const float* __restrict__ dI, const float* __restrict__ d
         glibc_sincosf_pair((float)(kTwoPiDt * (fpd + kDf15)), &sn, &cs); cd23.y = cs; sd23.y = sn;
     }
     v2f c01 = {1.0f, 1.0f}, c23 = c01, s01 = {0.0f, 0.0f}, s23 = s01;
-    ToneAcc acc;
+    ToneAcc<kFma> acc;
     acc.clear();
     for (int c = 0; c < kSps / kFsChunk; ++c) {
         __syncthreads();                                             // the previous chunk has been consumed
@@ -985,10 +1070,16 @@ void freq_drift_kernel(const float* __restrict__ dI, const float* __restrict__ d
 #pragma unroll 8
             for (int jj = 0; jj < kFsChunk; ++jj) {
                 if (c + jj > 0) {
+                    if constexpr (kFma) {
+                        const v2f n01 = fma2(c01, cd01, -(s01 * sd01)), n23 = fma2(c23, cd23, -(s23 * sd23));
+                        s01 = fma2(c01, sd01, s01 * cd01); s23 = fma2(c23, sd23, s23 * cd23);
+                        c01 = n01; c23 = n23;
+                    } else {
                     const v2f a01 = c01 * cd01, b01 = s01 * sd01, e01 = c01 * sd01, d01 = s01 * cd01;
                     const v2f a23 = c23 * cd23, b23 = s23 * sd23, e23 = c23 * sd23, d23 = s23 * cd23;
                     c01 = a01 - b01; s01 = e01 + d01;
                     c23 = a23 - b23; s23 = e23 + d23;
+                    }
                 }
                 acc.step(tile[sym][jj], make_float4(c01.x, c01.y, c23.x, c23.y), make_float4(s01.x, s01.y, s23.x, s23.y));
             }
@@ -1001,6 +1092,7 @@ void freq_drift_kernel(const float* __restrict__ dI, const float* __restrict__ d
 // one wave per candidate: lanes 0..4 fold one frequency hypothesis each (162 symbols in
 // order), lane 0 applies the strict '>' pick of wsprd.c:227-232 and updates the state, then --
 // if worth a try -- forms the jitter-0 soft symbols from the winner's amplitudes
+template <bool kFma>
 __global__ __launch_bounds__(64)
 void freq_metric_kernel(const float4* __restrict__ pw, FineState* __restrict__ items,
                         const int* __restrict__ item_list, int nshared, int ifmin, float fstep,
@@ -1032,7 +1124,7 @@ void freq_metric_kernel(const float4* __restrict__ pw, FineState* __restrict__ i
         float best = -1e30f, fbest = 0.0f;
         int bshift = 0, bf = -1;
         for (int f = 0; f < kNFreq; ++f)
-            if (met[f] > best) { best = met[f]; fbest = fin + (float)(ifmin + f) * fstep; bshift = st.shift; bf = f; }
+            if (met[f] > best) { best = met[f]; fbest = kFma ? fmaf1((float)(ifmin + f), fstep, fin) : fin + (float)(ifmin + f) * fstep; bshift = st.shift; bf = f; }
         st.freq = fbest;
         st.shift = bshift;
         st.sync = best;
@@ -1057,8 +1149,12 @@ void freq_metric_kernel(const float4* __restrict__ pw, FineState* __restrict__ i
             const float ff = f * f;
             f2sum += ff / 162.0f;
         }
+        if constexpr (kFma) {
+            fac_s = sqrtf(fmaf1(-fsum, fsum, f2sum));
+        } else {
         const float m2 = fsum * fsum;
         fac_s = sqrtf(f2sum - m2);
+        }
     }
     __syncthreads();
     const float fac = fac_s;
@@ -1097,6 +1193,7 @@ __global__ void pick_lag_kernel(FineState* __restrict__ items, int nitems,
 }
 
 // mode 1 epilogue: first frequency with the strictly largest metric
+template <bool kFma>
 __global__ void pick_freq_kernel(FineState* __restrict__ items, const int* __restrict__ item_list, int nitems,
                                  const float* __restrict__ sync_in, int nfreq, int ifmin, float fstep) {
     const int pos = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1108,7 +1205,7 @@ __global__ void pick_freq_kernel(FineState* __restrict__ items, const int* __res
     int bshift = 0;
     for (int q = 0; q < nfreq; ++q) {
         const float v = sync_in[(size_t)it * nfreq + q];
-        if (v > best) { best = v; fbest = fin + (float)(ifmin + q) * fstep; bshift = st.shift; }
+        if (v > best) { best = v; fbest = kFma ? fmaf1((float)(ifmin + q), fstep, fin) : fin + (float)(ifmin + q) * fstep; bshift = st.shift; }
     }
     st.freq = fbest;
     st.shift = bshift;
@@ -1120,21 +1217,20 @@ __global__ void pick_freq_kernel(FineState* __restrict__ items, const int* __res
 void launch_demod(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
                   int mode, int nlag, int lagstep, int ifmin, float fstep, const int* jitter,
                   float minsync1, float* sync_out, unsigned char* sym_out, float* rms_out,
-                  const DeviceTables& t, hipStream_t st, int symfac) {
+                  const DeviceTables& t, hipStream_t st, int symfac, int arith) {
     if (nitems <= 0 || nlag <= 0) return;
-    hipLaunchKernelGGL(demod_kernel, dim3(nlag, nitems), dim3(192), 0, st, dI, dQ, samples, items,
-                       (const int*)nullptr, mode, nlag, lagstep, ifmin, fstep, jitter, minsync1, sync_out,
+    hipLaunchKernelGGL(arith ? demod_kernel<true> : demod_kernel<false>, dim3(nlag, nitems), dim3(192), 0, st, dI, dQ,
+                       samples, items, (const int*)nullptr, mode, nlag, lagstep, ifmin, fstep, jitter, minsync1, sync_out,
                        sym_out, rms_out, t.sync, (float)symfac);
 }
-// Frequency scan (5 hypotheses at +-0.2 Hz, step 0.1) followed by the first ladder rung.
-// Drift-free candidates (list_shared) take the fused tiled path; drifting ones (list_own) the
-// general kernel.  Outputs: items[] updated (freq, sync), rung-0 sync/sym/rms at [item].
-void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int samples, FineState* items,
-                                     const int* list_shared, int n_shared, const int* list_own, int n_own,
-                                     int lagstep, float minsync1, const int* jitter0, float* tabs, float* pw,
-                                     float* scratch_sync, float* sync_out, unsigned char* sym_out,
-                                     float* rms_out, const DeviceTables& t, hipStream_t st,
-                                     const float* pw_lag, int nlag_lag) {
+namespace {
+template <bool kFma>
+void launch_freq_scan_t(const float* dI, const float* dQ, int samples, FineState* items,
+                        const int* list_shared, int n_shared, const int* list_own, int n_own,
+                        int lagstep, float minsync1, const int* jitter0, float* tabs, float* pw,
+                        float* scratch_sync, float* sync_out, unsigned char* sym_out,
+                        float* rms_out, const DeviceTables& t, hipStream_t st,
+                        const float* pw_lag, int nlag_lag) {
     // pw_lag (optional): the lag scan's amplitude block [item][nlag_lag][162] of the SAME items, still intact --
     // the centre hypothesis is read from it instead of being summed again; pw must then be a different buffer
     const float4* pl = reinterpret_cast<const float4*>(pw_lag);
@@ -1145,13 +1241,13 @@ void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int sampl
     static const bool nocentre = [] { const char* e = lab_env("WSPR_K4_FREQ"); return e && e[0] == 'n'; }();
     const int nlag_c = (pl && !nocentre) ? nlag_lag : 0;
     if (n_shared > 0) {
-        hipLaunchKernelGGL(phasor_freq_kernel, dim3(n_shared), dim3(64), 0, st, items, list_shared, -2, 0.1f, tabs);
+        hipLaunchKernelGGL(phasor_freq_kernel<kFma>, dim3(n_shared), dim3(64), 0, st, items, list_shared, -2, 0.1f, tabs);
         for (int r = 0; r < rep_freq; ++r)
-            hipLaunchKernelGGL(freq_scalar_kernel, dim3(n_shared), dim3(kFqThreads), 0, st, dI, dQ, samples, items,
+            hipLaunchKernelGGL(freq_scalar_kernel<kFma>, dim3(n_shared), dim3(kFqThreads), 0, st, dI, dQ, samples, items,
                                list_shared, tabs, reinterpret_cast<float4*>(pw), pl, nlag_c, lagstep);
-        hipLaunchKernelGGL(freq_centre_rare_kernel, dim3(n_shared), dim3(64), 0, st, dI, dQ, samples, items, list_shared,
+        hipLaunchKernelGGL(freq_centre_rare_kernel<kFma>, dim3(n_shared), dim3(64), 0, st, dI, dQ, samples, items, list_shared,
                            tabs, reinterpret_cast<float4*>(pw), nlag_c, lagstep);
-        hipLaunchKernelGGL(freq_metric_kernel, dim3(n_shared), dim3(64), 0, st,
+        hipLaunchKernelGGL(freq_metric_kernel<kFma>, dim3(n_shared), dim3(64), 0, st,
                            reinterpret_cast<const float4*>(pw), items, list_shared, n_shared, -2, 0.1f, minsync1,
                            sync_out, sym_out, rms_out, t.sync);
     }
@@ -1161,35 +1257,52 @@ void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int sampl
             // pw rows of the drifting candidates follow those of the drift-free ones
             float4* pw_own = reinterpret_cast<float4*>(pw) + (size_t)n_shared * kNFreq * kNSymD;
             for (int r = 0; r < rep_freq; ++r)
-            hipLaunchKernelGGL(freq_drift_kernel, dim3(n_own), dim3(kFsThreads), 0, st, dI, dQ, samples, items, list_own,
+            hipLaunchKernelGGL(freq_drift_kernel<kFma>, dim3(n_own), dim3(kFsThreads), 0, st, dI, dQ, samples, items, list_own,
                                -2, 0.1f, pw_own, nocentre ? nullptr : pl, nlag_lag, lagstep);
-            hipLaunchKernelGGL(freq_metric_kernel, dim3(n_own), dim3(64), 0, st, pw_own, items, list_own, n_own, -2, 0.1f,
+            hipLaunchKernelGGL(freq_metric_kernel<kFma>, dim3(n_own), dim3(64), 0, st, pw_own, items, list_own, n_own, -2, 0.1f,
                                minsync1, sync_out, sym_out, rms_out, t.sync);
             return;
         }
         // scratch_sync is indexed [item][5] by the general kernel
-        hipLaunchKernelGGL(demod_kernel, dim3(kNFreq, n_own), dim3(192), 0, st, dI, dQ, samples, items, list_own, 1,
+        hipLaunchKernelGGL(demod_kernel<kFma>, dim3(kNFreq, n_own), dim3(192), 0, st, dI, dQ, samples, items, list_own, 1,
                            kNFreq, lagstep, -2, 0.1f, (const int*)nullptr, 0.0f, scratch_sync, (unsigned char*)nullptr,
                            (float*)nullptr, t.sync, 50.0f);
-        hipLaunchKernelGGL(pick_freq_kernel, dim3((n_own + 63) / 64), dim3(64), 0, st, items, list_own, n_own,
+        hipLaunchKernelGGL(pick_freq_kernel<kFma>, dim3((n_own + 63) / 64), dim3(64), 0, st, items, list_own, n_own,
                            scratch_sync, kNFreq, -2, 0.1f);
-        hipLaunchKernelGGL(demod_kernel, dim3(1, n_own), dim3(192), 0, st, dI, dQ, samples, items, list_own, 2, 1,
+        hipLaunchKernelGGL(demod_kernel<kFma>, dim3(1, n_own), dim3(192), 0, st, dI, dQ, samples, items, list_own, 2, 1,
                            lagstep, 0, 0.0f, jitter0, minsync1, sync_out, sym_out, rms_out, t.sync, 50.0f);
     }
 }
+}  // namespace
 
-void launch_phasor_tables(const FineState* items, int nitems, int mode, float* tabs, hipStream_t st) {
-    if (nitems <= 0) return;
-    hipLaunchKernelGGL(phasor_table_kernel, dim3(1, nitems), dim3(64), 0, st, items, mode, tabs);
+// Frequency scan (5 hypotheses at +-0.2 Hz, step 0.1) followed by the first ladder rung.
+// Drift-free candidates (list_shared) take the fused tiled path; drifting ones (list_own) the
+// general kernel.  Outputs: items[] updated (freq, sync), rung-0 sync/sym/rms at [item].
+void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int samples, FineState* items,
+                                     const int* list_shared, int n_shared, const int* list_own, int n_own,
+                                     int lagstep, float minsync1, const int* jitter0, float* tabs, float* pw,
+                                     float* scratch_sync, float* sync_out, unsigned char* sym_out,
+                                     float* rms_out, const DeviceTables& t, hipStream_t st,
+                                     const float* pw_lag, int nlag_lag, int arith) {
+    if (arith) launch_freq_scan_t<true>(dI, dQ, samples, items, list_shared, n_shared, list_own, n_own, lagstep, minsync1,
+                                        jitter0, tabs, pw, scratch_sync, sync_out, sym_out, rms_out, t, st, pw_lag, nlag_lag);
+    else launch_freq_scan_t<false>(dI, dQ, samples, items, list_shared, n_shared, list_own, n_own, lagstep, minsync1,
+                                   jitter0, tabs, pw, scratch_sync, sync_out, sym_out, rms_out, t, st, pw_lag, nlag_lag);
 }
 
-// item_list_shared / item_list_own: indices into items[] of the candidates without / with drift
-void launch_demod_tiled(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
-                        const int* list_shared, int n_shared, const int* list_own, int n_own, int mode,
-                        int nlag, int lagstep, float minsync1, const float* tabs, float* pw,
-                        float* sync_out, unsigned char* sym_out, float* rms_out,
-                        const DeviceTables& t, hipStream_t st) {
+void launch_phasor_tables(const FineState* items, int nitems, int mode, float* tabs, hipStream_t st, int arith) {
     if (nitems <= 0) return;
+    hipLaunchKernelGGL(arith ? phasor_table_kernel<true> : phasor_table_kernel<false>, dim3(1, nitems), dim3(64), 0, st,
+                       items, mode, tabs);
+}
+
+namespace {
+template <bool kFma>
+void launch_demod_tiled_t(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
+                          const int* list_shared, int n_shared, const int* list_own, int n_own, int mode,
+                          int nlag, int lagstep, float minsync1, const float* tabs, float* pw,
+                          float* sync_out, unsigned char* sym_out, float* rms_out,
+                          const DeviceTables& t, hipStream_t st) {
     auto tile_bytes = [&](int syms) {
         const int span = kSps * syms + lagstep * (nlag - 1);
         const int pitch = (span + lagstep - 1) / lagstep + 1;
@@ -1207,18 +1320,18 @@ void launch_demod_tiled(const float* dI, const float* dQ, int samples, const Fin
     do {                                                                                                         \
         if (n_shared > 0 && STEP == 8 && nlag == 33 && mode == 0 && lagsys_kernel)                               \
             for (int r_ = 0; r_ < rep_lag; ++r_)                                                                 \
-            hipLaunchKernelGGL(demod_lagsys_kernel, dim3(kSysWaves * ((n_shared + 7) & ~7) + (n_shared + 63) / 64), dim3(64), 0, st, \
+            hipLaunchKernelGGL(demod_lagsys_kernel<kFma>, dim3(kSysWaves * ((n_shared + 7) & ~7) + (n_shared + 63) / 64), dim3(64), 0, st, \
                                dI, dQ, samples, items, list_shared, n_shared, tabs, pw4);                        \
         else if (n_shared > 0)                                                                                   \
-            hipLaunchKernelGGL((demod_tile_kernel<STEP, true>), dim3(kNSymD / kTileSymsShared, n_shared),        \
+            hipLaunchKernelGGL((demod_tile_kernel<STEP, true, kFma>), dim3(kNSymD / kTileSymsShared, n_shared),        \
                                threads(kTileSymsShared), tile_bytes(kTileSymsShared), st, dI, dQ, samples,        \
                                items, list_shared, mode, nlag, minsync1, tabs, pw4);                             \
         if (n_own > 0 && STEP == 8 && nlag == 33 && mode == 0 && drift_kernel)                                   \
             for (int r_ = 0; r_ < rep_lag; ++r_)                                                                 \
-            hipLaunchKernelGGL(demod_drift_kernel, dim3((kNSymD + kDrSyms - 1) / kDrSyms, n_own), dim3(64), 0, st, \
+            hipLaunchKernelGGL(demod_drift_kernel<kFma>, dim3((kNSymD + kDrSyms - 1) / kDrSyms, n_own), dim3(64), 0, st, \
                                dI, dQ, samples, items, list_own, pw4);                                           \
         else if (n_own > 0)                                                                                      \
-            hipLaunchKernelGGL((demod_tile_kernel<STEP, false>), dim3(kNSymD / kTileSymsOwn, n_own),             \
+            hipLaunchKernelGGL((demod_tile_kernel<STEP, false, kFma>), dim3(kNSymD / kTileSymsOwn, n_own),             \
                                threads(kTileSymsOwn), kTileSymsOwn * kOwnTabPitch * 16 + tile_bytes(kTileSymsOwn), st, dI, dQ, \
                                samples, items, list_own, mode, nlag, minsync1, tabs, pw4);                       \
     } while (0)
@@ -1226,8 +1339,22 @@ void launch_demod_tiled(const float* dI, const float* dQ, int samples, const Fin
     else if (lagstep == 16) WSPR_LAUNCH_TILE(16);
     else WSPR_LAUNCH_TILE(3);
 #undef WSPR_LAUNCH_TILE
-    hipLaunchKernelGGL(demod_metric_kernel, dim3((nitems * nlag + 63) / 64), dim3(64), 0, st, pw4, items, nitems,
+    hipLaunchKernelGGL(demod_metric_kernel<kFma>, dim3((nitems * nlag + 63) / 64), dim3(64), 0, st, pw4, items, nitems,
                        mode, nlag, minsync1, sync_out, sym_out, rms_out, t.sync);
+}
+}  // namespace
+
+// item_list_shared / item_list_own: indices into items[] of the candidates without / with drift
+void launch_demod_tiled(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
+                        const int* list_shared, int n_shared, const int* list_own, int n_own, int mode,
+                        int nlag, int lagstep, float minsync1, const float* tabs, float* pw,
+                        float* sync_out, unsigned char* sym_out, float* rms_out,
+                        const DeviceTables& t, hipStream_t st, int arith) {
+    if (nitems <= 0) return;
+    if (arith) launch_demod_tiled_t<true>(dI, dQ, samples, items, nitems, list_shared, n_shared, list_own, n_own, mode, nlag,
+                                          lagstep, minsync1, tabs, pw, sync_out, sym_out, rms_out, t, st);
+    else launch_demod_tiled_t<false>(dI, dQ, samples, items, nitems, list_shared, n_shared, list_own, n_own, mode, nlag,
+                                     lagstep, minsync1, tabs, pw, sync_out, sym_out, rms_out, t, st);
 }
 
 #ifdef WSPR_LAB   // calibration kernel: lab build only
@@ -1269,9 +1396,9 @@ void launch_pick_lag(FineState* items, int nitems, const float* sync_in, int nla
     hipLaunchKernelGGL(pick_lag_kernel, dim3((nitems + 63) / 64), dim3(64), 0, st, items, nitems, sync_in, nlag, lagstep);
 }
 void launch_pick_freq(FineState* items, int nitems, const float* sync_in, int nfreq, int ifmin,
-                      float fstep, hipStream_t st) {
+                      float fstep, hipStream_t st, int arith) {
     if (nitems <= 0) return;
-    hipLaunchKernelGGL(pick_freq_kernel, dim3((nitems + 63) / 64), dim3(64), 0, st, items, (const int*)nullptr,
+    hipLaunchKernelGGL(arith ? pick_freq_kernel<true> : pick_freq_kernel<false>, dim3((nitems + 63) / 64), dim3(64), 0, st, items, (const int*)nullptr,
                        nitems, sync_in, nfreq, ifmin, fstep);
 }
 

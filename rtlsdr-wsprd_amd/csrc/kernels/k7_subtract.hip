@@ -155,6 +155,10 @@ constexpr int kHalo = kLpfTaps / 2;                               // 180 samples
 // for the epilogue.  Set 3.13 -> 2.89 ms per 2 048 jobs, 664 KB of scratch per job gone.
 // Staging goes symbol by symbol (thread j = sample j of the symbol), so that a wave sits in ONE symbol and fetches
 // its few runs with wave-uniform (scalar) loads.
+// kFma (wspr_set_arithmetic): the contracted mode fuses the three sites of wsprd.c:378-409 as clang's -ffp-contract=on
+// does, left product first: ci = fma(x, cr, y*sr), cq = fma(y, cr, -(x*sr)); cfi = fma(w, ci, cfi) (one v_pk_fma_f32 per
+// tap and output pair); ri = fma(cfi, refi, -(cfq*refq)), rq = fma(cfi, refq, cfq*refi).
+template <bool kFma>
 __global__ __launch_bounds__(kFirThreads)
 void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np,
                           const SubJob* __restrict__ jobs, const PhaseTable* __restrict__ tables,
@@ -225,9 +229,14 @@ void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np
         float a = 0.0f, b = 0.0f;
         if (k > 0 && k < np) {
             const float x = xi[k], y = xq[k];
+            if constexpr (kFma) {
+                a = __builtin_fmaf(x, cr, y * sr);
+                b = __builtin_fmaf(y, cr, -(x * sr));
+            } else {
             const float p1 = x * cr, p2 = y * sr, p3 = y * cr, p4 = x * sr;
             a = p1 + p2;                  // Re{s conj(r)}
             b = p3 - p4;                  // Im{s conj(r)}
+            }
         }
         const int e = n - n_lo;
         tile[(e & 7) * kFir8Pitch + (e >> 3)] = make_float2(a, b);
@@ -271,6 +280,14 @@ void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const v2f wu = {w[u], w[u]};
+            if constexpr (kFma) {
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    const int i = (u + r) & 7;
+                    acc[r] = __builtin_elementwise_fma(wu, i < u ? in[i] : old[i], acc[r]);
+                }
+                continue;
+            }
             v2f p[8];
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
@@ -307,8 +324,14 @@ void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np
         if (k > 0 && k < np) {
             const float2 rr = rref[8 * tid + r];
             const float si = acc[r].x, sq = acc[r].y;
+            float ri, rq;
+            if constexpr (kFma) {
+                ri = __builtin_fmaf(si, rr.x, -(sq * rr.y));
+                rq = __builtin_fmaf(si, rr.y, sq * rr.x);
+            } else {
             const float a = si * rr.x, b = sq * rr.y, c = si * rr.y, d = sq * rr.x;
-            float ri = a - b, rq = c + d;
+            ri = a - b; rq = c + d;
+            }
             if (edge_tile) {
                 float norm = 1.0f;
                 if (n < kLpfTaps / 2)                    norm = lpf_part[kLpfTaps / 2 + n];
@@ -404,14 +427,15 @@ void launch_subtract_symbolwise(float* dI, float* dQ, int samples, float f0, int
 size_t subtract_scratch_floats(int njobs) { return (size_t)njobs * (kTableFloats + (size_t)kFirWgs * 2 * kHalo * 2); }
 
 void launch_subtract(float* dI, float* dQ, int samples, const SubJob* jobs, int njobs,
-                     float* scratch, const DeviceTables& t, hipStream_t st) {
+                     float* scratch, const DeviceTables& t, hipStream_t st, int arith) {
     if (njobs <= 0) return;
     PhaseTable* tables = reinterpret_cast<PhaseTable*>(scratch);
     float2* halo = reinterpret_cast<float2*>(scratch + (size_t)njobs * kTableFloats);
     hipLaunchKernelGGL(sub_runs_wave_kernel, dim3(njobs), dim3(64), 0, st, jobs, njobs, tables);
-    hipLaunchKernelGGL(sub_fir_fused_kernel, dim3((kFirWgs + 1) / 2, njobs), dim3(kFirThreads), 0, st,
+    auto fir = arith ? sub_fir_fused_kernel<true> : sub_fir_fused_kernel<false>;
+    hipLaunchKernelGGL(fir, dim3((kFirWgs + 1) / 2, njobs), dim3(kFirThreads), 0, st,
                        dI, dQ, samples, jobs, tables, t.lpf, t.lpf_part, halo, 0);
-    hipLaunchKernelGGL(sub_fir_fused_kernel, dim3(kFirWgs / 2, njobs), dim3(kFirThreads), 0, st,
+    hipLaunchKernelGGL(fir, dim3(kFirWgs / 2, njobs), dim3(kFirThreads), 0, st,
                        dI, dQ, samples, jobs, tables, t.lpf, t.lpf_part, halo, 1);
 }
 

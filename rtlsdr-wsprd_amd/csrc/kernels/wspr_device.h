@@ -88,11 +88,14 @@ struct DeviceTables {
 };
 
 // ---- launchers (all asynchronous on `st`) ----------------------------------
+// `arith` (wspr_set_arithmetic, read once per call): 0 = WSPR_ARITH_EXACT, the reference's separately rounded
+// multiplies and adds; 1 = WSPR_ARITH_CONTRACTED, the fusions clang's -ffp-contract=on makes in wsprd.c.  Launchers of
+// kernels without such a site take no `arith`.
 void launch_fft_bank(const float* dI, const float* dQ, const int* seg_list, int nseg_active,
-                     int samples, float* ps, const DeviceTables& t, hipStream_t st);
+                     int samples, float* ps, const DeviceTables& t, hipStream_t st, int arith);
 // K1 fused with the time average (one workgroup per segment): ps as above, psavg[seg][kPsStride]
 void launch_fft_bank_avg(const float* dI, const float* dQ, const int* seg_list, int nseg_active,
-                         int samples, float* ps, float* psavg, const DeviceTables& t, hipStream_t st);
+                         int samples, float* ps, float* psavg, const DeviceTables& t, hipStream_t st, int arith);
 void launch_calib_copy(const float* src, float* dst, size_t n, hipStream_t st);
 void launch_calib_copy16(const float* src, float* dst, size_t n, hipStream_t st, int variant = 0);
 
@@ -126,17 +129,17 @@ void launch_coarse_sync(const float* ps, const int* seg_list, int nseg_active, i
 void launch_demod(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
                   int mode, int nhyp, int lagstep, int ifmin, float fstep, const int* jitter,
                   float minsync1, float* sync_out, unsigned char* sym_out, float* rms_out,
-                  const DeviceTables& t, hipStream_t st, int symfac = 50);
+                  const DeviceTables& t, hipStream_t st, int symfac, int arith);
 // Tiled fast path for the wide searches.  FineState.pad must hold the index of the item's
 // first phasor table in `tabs` (1 table if drift == 0, else 162); list_shared/list_own are the
 // item indices without / with drift.  mode 0: nlag lags shift_coarse-128 + lagstep*m;
 // mode 2: 43 lags shift-63+3*m (lagstep must be 3).  pw: nitems*nlag*162 float4 of scratch.
-void launch_phasor_tables(const FineState* items, int nitems, int mode, float* tabs, hipStream_t st);
+void launch_phasor_tables(const FineState* items, int nitems, int mode, float* tabs, hipStream_t st, int arith);
 void launch_demod_tiled(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
                         const int* list_shared, int n_shared, const int* list_own, int n_own, int mode,
                         int nlag, int lagstep, float minsync1, const float* tabs, float* pw,
                         float* sync_out, unsigned char* sym_out, float* rms_out,
-                        const DeviceTables& t, hipStream_t st);
+                        const DeviceTables& t, hipStream_t st, int arith);
 // mode 1 (5 frequencies) + first ladder rung; see k4_demod.hip.  tabs: n_shared*5 tables,
 // pw: n_shared*5*162 float4, scratch_sync: nitems*5 floats.
 void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int samples, FineState* items,
@@ -144,13 +147,14 @@ void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int sampl
                                      int lagstep, float minsync1, const int* jitter0, float* tabs, float* pw,
                                      float* scratch_sync, float* sync_out, unsigned char* sym_out,
                                      float* rms_out, const DeviceTables& t, hipStream_t st,
-                                     const float* pw_lag = nullptr, int nlag_lag = 0);
+                                     const float* pw_lag, int nlag_lag, int arith);
 void launch_pick_lag(FineState* items, int nitems, const float* sync_in, int nlag, int lagstep, hipStream_t st);
 void launch_pick_freq(FineState* items, int nitems, const float* sync_in, int nfreq, int ifmin,
-                      float fstep, hipStream_t st);
+                      float fstep, hipStream_t st, int arith);
 size_t subtract_scratch_floats(int njobs);
 void launch_subtract(float* dI, float* dQ, int samples, const SubJob* jobs, int njobs,
-                     float* scratch /* subtract_scratch_floats(njobs) */, const DeviceTables& t, hipStream_t st);
+                     float* scratch /* subtract_scratch_floats(njobs) */, const DeviceTables& t, hipStream_t st,
+                     int arith);
 // subtract_signal() of the reference (wsprd.c:263-312): one segment row, symbols in device memory
 void launch_subtract_symbolwise(float* dI, float* dQ, int samples, float f0, int shift, float drift,
                                 const unsigned char* d_sym, hipStream_t st);

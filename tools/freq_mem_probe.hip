@@ -25,15 +25,15 @@ int main() {
             items[i] = f;
         }
         OK(hipMemcpy(dit, items.data(), n * sizeof(FineState), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(phasor_freq_kernel, dim3(n), dim3(64), 0, 0, dit, dl, -2, 0.1f, tabs);
+        hipLaunchKernelGGL(phasor_freq_kernel<false>, dim3(n), dim3(64), 0, 0, dit, dl, -2, 0.1f, tabs);
         for (int which = 0; which < 2; ++which)
             for (int rep = 0; rep < 3; ++rep) {
                 OK(hipEventRecord(e0, 0));
                 for (int k = 0; k < 10; ++k) {
                     if (which == 0)
-                        hipLaunchKernelGGL(freq_scalar_kernel, dim3(n), dim3(kFqThreads), 0, 0, dI, dQ, np, dit, dl, tabs, pw, (const float4*)nullptr, 0, 8);
+                        hipLaunchKernelGGL(freq_scalar_kernel<false>, dim3(n), dim3(kFqThreads), 0, 0, dI, dQ, np, dit, dl, tabs, pw, (const float4*)nullptr, 0, 8);
                     else
-                        hipLaunchKernelGGL(freq_scalar_kernel, dim3(n), dim3(kFqThreads), 0, 0, dI, dQ, np, dit, dl, tabs, pw, (const float4*)nullptr, 0, 8);
+                        hipLaunchKernelGGL(freq_scalar_kernel<false>, dim3(n), dim3(kFqThreads), 0, 0, dI, dQ, np, dit, dl, tabs, pw, (const float4*)nullptr, 0, 8);
                 }
                 OK(hipEventRecord(e1, 0)); OK(hipEventSynchronize(e1));
                 float ms; OK(hipEventElapsedTime(&ms, e0, e1));

@@ -1,6 +1,6 @@
 // Unit check of demod_lagsys_kernel against demod_tile_kernel<8, true> (one (symbol, lag) per lane, samples in LDS: the
 // kernel quick mode and WSPR_K4_LAG=tile use) -- same amplitudes, bit for bit -- on random data, incl. candidates
-// that hang over either end of the record.  Includes the kernel file itself (its kernels live in an anonymous namespace).
+// that hang over either end of the record.  Includes the kernel file itself (its kernels live in an anonymous namespace).  Both arithmetic modes (kFma).
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I rtlsdr-wsprd_amd/csrc/kernels tools/lagsys_check.hip -o tools/lagsys_check.bin
 #include "../rtlsdr-wsprd_amd/csrc/kernels/k4_demod.hip"
 #include <cstdio>
@@ -31,13 +31,13 @@ int main(int argc, char** argv) {
     OK(hipMemcpy(dI, I.data(), I.size() * 4, hipMemcpyHostToDevice)); OK(hipMemcpy(dQ, Q.data(), Q.size() * 4, hipMemcpyHostToDevice));
     OK(hipMemcpy(dit, items.data(), n * sizeof(FineState), hipMemcpyHostToDevice)); OK(hipMemcpy(dl, list.data(), n * 4, hipMemcpyHostToDevice));
     OK(hipMemset(pa, 0xff, npw * 16)); OK(hipMemset(pb, 0xee, npw * 16));
-    hipLaunchKernelGGL(phasor_table_kernel, dim3(1, n), dim3(64), 0, 0, dit, 0, tabs);
+    hipLaunchKernelGGL(phasor_table_kernel<false>, dim3(1, n), dim3(64), 0, 0, dit, 0, tabs);
     const int span = kSps * kTileSymsShared + 8 * 32, pitch = (span + 7) / 8 + 1;
     const size_t tile_bytes = (size_t)pitch * 8 * sizeof(float2);
     const dim3 tile_threads(((kTileSymsShared * 33 + 63) / 64) * 64);
-    hipLaunchKernelGGL((demod_tile_kernel<8, true>), dim3(kNSymD / kTileSymsShared, n), tile_threads, tile_bytes, 0, dI, dQ, np, dit,
+    hipLaunchKernelGGL((demod_tile_kernel<8, true, false>), dim3(kNSymD / kTileSymsShared, n), tile_threads, tile_bytes, 0, dI, dQ, np, dit,
                        dl, 0, 33, 0.0f, tabs, pa);
-    hipLaunchKernelGGL(demod_lagsys_kernel, dim3(kSysWaves * ((n + 7) & ~7) + (n + 63) / 64), dim3(64), 0, 0, dI, dQ, np, dit, dl, n, tabs, pb);
+    hipLaunchKernelGGL(demod_lagsys_kernel<false>, dim3(kSysWaves * ((n + 7) & ~7) + (n + 63) / 64), dim3(64), 0, 0, dI, dQ, np, dit, dl, n, tabs, pb);
     OK(hipDeviceSynchronize());
     std::vector<float> a(npw * 4), b(npw * 4);
     OK(hipMemcpy(a.data(), pa, npw * 16, hipMemcpyDeviceToHost)); OK(hipMemcpy(b.data(), pb, npw * 16, hipMemcpyDeviceToHost));
@@ -56,6 +56,21 @@ int main(int argc, char** argv) {
         bad += badi;
     }
     printf(bad ? "MISMATCH\n" : "lagsys == tile kernel bit for bit\n");
+    {   // the contracted instantiations (wspr_set_arithmetic): the same comparison, fused arithmetic in both kernels
+        OK(hipMemset(pa, 0xff, npw * 16)); OK(hipMemset(pb, 0xee, npw * 16));
+        hipLaunchKernelGGL(phasor_table_kernel<true>, dim3(1, n), dim3(64), 0, 0, dit, 0, tabs);
+        hipLaunchKernelGGL((demod_tile_kernel<8, true, true>), dim3(kNSymD / kTileSymsShared, n), tile_threads, tile_bytes, 0, dI, dQ,
+                           np, dit, dl, 0, 33, 0.0f, tabs, pa);
+        hipLaunchKernelGGL(demod_lagsys_kernel<true>, dim3(kSysWaves * ((n + 7) & ~7) + (n + 63) / 64), dim3(64), 0, 0, dI, dQ, np, dit,
+                           dl, n, tabs, pb);
+        OK(hipDeviceSynchronize());
+        OK(hipMemcpy(a.data(), pa, npw * 16, hipMemcpyDeviceToHost)); OK(hipMemcpy(b.data(), pb, npw * 16, hipMemcpyDeviceToHost));
+        long badf = 0;
+        for (size_t o = 0; o < npw * 4; o += 4) badf += memcmp(&a[o], &b[o], 16) != 0;
+        if (badf) printf("MISMATCH (contracted): %ld of %zu amplitudes differ\n", badf, npw);
+        else printf("contracted: lagsys == tile kernel bit for bit\n");
+        bad += badf;
+    }
     {   // timing on many candidates (the same 8 items repeated)
         const int nb = 2048;
         std::vector<int> big(nb);
@@ -65,13 +80,13 @@ int main(int argc, char** argv) {
         for (int rep = 0; rep < 2; ++rep) {
             OK(hipEventRecord(e0, 0));
             for (int k = 0; k < 5; ++k)
-                hipLaunchKernelGGL(demod_lagsys_kernel, dim3(kSysWaves * ((nb + 7) & ~7) + (nb + 63) / 64), dim3(64), 0, 0, dI, dQ, np, dit, dbl, nb, tabs, pb);
+                hipLaunchKernelGGL(demod_lagsys_kernel<false>, dim3(kSysWaves * ((nb + 7) & ~7) + (nb + 63) / 64), dim3(64), 0, 0, dI, dQ, np, dit, dbl, nb, tabs, pb);
             OK(hipEventRecord(e1, 0)); OK(hipEventSynchronize(e1));
             float ms; OK(hipEventElapsedTime(&ms, e0, e1));
             printf("lagsys: %.3f ms per 2048 candidates (two cached segments)\n", ms / 5);
             OK(hipEventRecord(e0, 0));
             for (int k = 0; k < 5; ++k)
-                hipLaunchKernelGGL((demod_tile_kernel<8, true>), dim3(kNSymD / kTileSymsShared, nb), tile_threads, tile_bytes, 0, dI, dQ,
+                hipLaunchKernelGGL((demod_tile_kernel<8, true, false>), dim3(kNSymD / kTileSymsShared, nb), tile_threads, tile_bytes, 0, dI, dQ,
                                    np, dit, dbl, 0, 33, 0.0f, tabs, pa);
             OK(hipEventRecord(e1, 0)); OK(hipEventSynchronize(e1));
             OK(hipEventElapsedTime(&ms, e0, e1));
