@@ -269,12 +269,16 @@ class BatchDecoder:
         return int(sum(self.nres))
 
 
+# wspr_last_timings(): one name per value, in the order include/wspr_mi355x.h documents (csrc/host/wspr_pipeline.h: TimingSlot)
+TIMING_NAMES = (
+    "fft_sync_ms", "host_bookkeeping_ms", "device_fano_tail_ms", "demod_ms", "subtract_ms", "host_fano_ms",
+    "total_ms", "fano_calls", "fano_timeouts", "fano_cycles", "candidates_refined", "gpu_waves",
+    "fano_left_to_device", "segments_redecoded", "candidates_consumed", "subtractions",
+    "cpu_ms_call", "cpu_ms_pass_start", "cpu_ms_build_wave", "cpu_ms_refine", "cpu_ms_ladder", "cpu_ms_books",
+    "cpu_ms_subtract", "cpu_ms_finish", "message_cache_lookups", "message_cache_hits")
+
+
 def last_timings():
-    ms = (C.c_double * 26)()
-    n = lib().wspr_last_timings(C.addressof(ms), 26)
-    names = ["fft_sync_ms", "host_bookkeeping_ms", "device_fano_tail_ms", "demod_ms", "subtract_ms", "host_fano_ms",
-             "total_ms", "fano_calls", "fano_timeouts", "fano_cycles", "candidates_refined", "gpu_waves",
-             "fano_left_to_device", "segments_redecoded", "candidates_consumed", "subtractions",
-             "cpu_ms_call", "cpu_ms_pass_start", "cpu_ms_build_wave", "cpu_ms_refine", "cpu_ms_ladder", "cpu_ms_books",
-             "cpu_ms_subtract", "cpu_ms_finish", "message_cache_lookups", "message_cache_hits"]
-    return {names[i]: ms[i] for i in range(n)}
+    ms = (C.c_double * len(TIMING_NAMES))()
+    n = lib().wspr_last_timings(C.addressof(ms), len(TIMING_NAMES))
+    return {TIMING_NAMES[i]: ms[i] for i in range(n)}

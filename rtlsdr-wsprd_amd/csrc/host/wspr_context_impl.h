@@ -1,4 +1,4 @@
-// Internals shared by the two host translation units of the scheduler (wspr_context.hip: contexts, lanes, buffers,
+// Internals shared by the two translation units of the host scheduler (wspr_context.hip: contexts, lanes, buffers,
 // loads, front end, single-call stages; wspr_pipeline.hip: the decode itself): how a host thread waits, grow-only
 // buffers, the fork-join pool, the context's state, the CPUs a rank may count on.  Not part of any interface.
 #pragma once
@@ -266,7 +266,7 @@ struct Context::Impl {
     // host-side per-segment callsign hash memory (reference: locals of wspr_decode)
     char* hash_arena = nullptr;
     size_t hash_arena_segs = 0;
-    double t_ms[26] = {0};           // stage times (ms), Fano statistics and host CPU time by phase of the last batch
+    double t_ms[kTimingSlots] = {0};           // stage times (ms), Fano statistics and host CPU time by phase of the last batch
     std::atomic<long> n_fano{0}, n_timeout{0}, n_cycles{0}, n_kept{0}, n_subjobs{0}, n_mc_lookups{0}, n_mc_hits{0};
     bool blocking = false;
     hipEvent_t ev_sync = nullptr;

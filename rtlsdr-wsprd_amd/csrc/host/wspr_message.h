@@ -4,7 +4,7 @@
 // the HIP pipeline hands it soft symbols and receives channel symbols back.
 //
 // Reference interfaces mirrored (same names are exported with C linkage from
-// wspr_capi.cpp): wsprd/fano.h:14-28, wsprd/wsprd_utils.h:32-42,
+// wspr_capi_reference.hip): wsprd/fano.h:14-28, wsprd/wsprd_utils.h:32-42,
 // wsprd/wsprsim_utils.h:1-9, wsprd/nhash.h:3.
 #pragma once
 #include <cstddef>

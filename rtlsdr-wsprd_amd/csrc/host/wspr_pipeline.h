@@ -43,6 +43,24 @@ struct ArithScope {
     ArithScope& operator=(const ArithScope&) = delete;
 };
 
+// The values of wspr_last_timings(), in the order include/wspr_mi355x.h documents (that order is ABI; the Python
+// wrapper's TIMING_NAMES repeats it).  A new value goes at the end, here and in both of those.
+enum TimingSlot : int {
+    kTmFftSyncMs = 0, kTmHostBookkeepingMs, kTmDeviceFanoTailMs, kTmDemodMs, kTmSubtractMs, kTmHostFanoMs, kTmTotalMs,
+    kTmFanoCalls, kTmFanoTimeouts, kTmFanoCycles, kTmCandidatesRefined, kTmGpuWaves, kTmFanoLeftToDevice,
+    kTmSegmentsRedecoded, kTmCandidatesConsumed, kTmSubtractions,
+    kTmCpuMsCall, kTmCpuMsPassStart, kTmCpuMsBuildWave, kTmCpuMsRefine, kTmCpuMsLadder, kTmCpuMsBooks, kTmCpuMsSubtract,
+    kTmCpuMsFinish,
+    kTmMessageCacheLookups, kTmMessageCacheHits,
+    kTimingSlots
+};
+// A batch runs on several pipelines at once and each keeps its own values; wspr_last_timings() folds them.  The stage
+// times and the wall time before this index overlap between pipelines: the call's figure is the MAXIMUM.  Everything
+// from it on is SUMMED -- the counts, and the CPU times kTmCpuMs* as well (CPU time spent on different threads adds
+// up; the public header says "summed over the slots").
+constexpr int kTimingFirstSummed = kTmFanoCalls;
+static_assert(kTimingSlots == 26 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
+
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt
     std::vector<unsigned char> sym;       // 162 soft symbols each, transmission order

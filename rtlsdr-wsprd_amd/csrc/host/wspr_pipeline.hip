@@ -224,7 +224,7 @@ int Context::decode_resident(int nseg, int samples, const decoder_options& opt, 
     for (double& v : c.t_ms) v = 0.0;
     c.n_fano = 0; c.n_timeout = 0; c.n_cycles = 0; c.n_kept = 0; c.n_subjobs = 0; c.n_mc_lookups = 0; c.n_mc_hits = 0;
     const auto t_all0 = std::chrono::steady_clock::now();
-    CpuSpan cpu_all(&c.t_ms[16]);
+    CpuSpan cpu_all(&c.t_ms[kTmCpuMsCall]);
     t_spin_us = nseg <= 128 ? 600 : 40;      // a call of up to a hundred segments is a few milliseconds: its waits poll (lone 17-127-segment calls: 1.7-2.8 -> 1.3-2.3 ms)
     for (int s = 0; s < nseg; ++s) n_results[s] = 0;
     const int blocks = 4 * (samples / kFftSize) - 1;
@@ -261,10 +261,10 @@ int Context::decode_resident(int nseg, int samples, const decoder_options& opt, 
             c.n_fano++; c.n_cycles += cyc[i];
             if (ret[i] == 0) dirty[pend.seg[i]] = 1; else c.n_timeout++;
         }
-        c.t_ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_t0).count();
+        c.t_ms[kTmDeviceFanoTailMs] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_t0).count();
         std::vector<int> redo;
         for (int s = 0; s < nseg; ++s) if (dirty[s]) redo.push_back(s);
-        c.t_ms[12] = np; c.t_ms[13] = (double)redo.size();
+        c.t_ms[kTmFanoLeftToDevice] = np; c.t_ms[kTmSegmentsRedecoded] = (double)redo.size();
         if (!redo.empty()) {
             // ---- exact re-decode of the few segments where a late success changes the story ----
             reload(redo);
@@ -275,14 +275,14 @@ int Context::decode_resident(int nseg, int samples, const decoder_options& opt, 
             decode_core(nseg, samples, opt, out, max_results, n_results, redo, 0u, none, &memo);
         }
     }
-    c.t_ms[6] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all0).count();
-    c.t_ms[7] = (double)c.n_fano.load();
-    c.t_ms[8] = (double)c.n_timeout.load();
-    c.t_ms[9] = (double)c.n_cycles.load();
-    c.t_ms[14] = (double)c.n_kept.load();                 // refined candidates whose result was consumed (the rest: cut speculation)
-    c.t_ms[15] = (double)c.n_subjobs.load();
-    c.t_ms[24] = (double)c.n_mc_lookups.load();           // the books are kept by the pool's threads: atomic counts
-    c.t_ms[25] = (double)c.n_mc_hits.load();
+    c.t_ms[kTmTotalMs] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_all0).count();
+    c.t_ms[kTmFanoCalls] = (double)c.n_fano.load();
+    c.t_ms[kTmFanoTimeouts] = (double)c.n_timeout.load();
+    c.t_ms[kTmFanoCycles] = (double)c.n_cycles.load();
+    c.t_ms[kTmCandidatesConsumed] = (double)c.n_kept.load();   // refined candidates whose result was consumed (the rest: cut speculation)
+    c.t_ms[kTmSubtractions] = (double)c.n_subjobs.load();
+    c.t_ms[kTmMessageCacheLookups] = (double)c.n_mc_lookups.load();   // the books are kept by the pool's threads: atomic counts
+    c.t_ms[kTmMessageCacheHits] = (double)c.n_mc_hits.load();
     c.crowded = c.n_timeout.load() * 10 > nseg;
     return 0;
 }
@@ -368,6 +368,15 @@ struct Context::DecodeRun {
             c.hash_arena_segs = 1;
         }
     }
+    // the Fano gate (wsprd.c:758) on entry g of the block that came down last (h_sync / h_rms)
+    bool gated(size_t g) const { return h_sync[g] > minsync2 && h_rms[g] > minrms; }
+    // rung r of the rest of the ladder = lag index (jitter + 63) / 3 of the 43-lag block of remaining_rungs()
+    int ladder_lag(int r) const { return (c.jitter_ladder[r + 1] + 63) / 3; }
+    static void take_device_result(WaveItem& w, bool decoded, unsigned cycles, const unsigned char* data10) {
+        w.decoded = decoded; w.cycles = cycles;
+        memset(w.decdata, 0, sizeof w.decdata);
+        memcpy(w.decdata, data10, 10);
+    }
     char* hashtab_of(int s) const { return c.hash_arena + (size_t)s * per_seg; }
     char* loctab_of(int s) const { return c.hash_arena + (size_t)s * per_seg + (size_t)kHashSlots * kHashWidth; }
 
@@ -428,7 +437,7 @@ void Context::DecodeRun::start_pass(int pass, const std::vector<int>& active) {
         upload(d_seglist, h, (size_t)nact * 4, c.stream);
     }
     {
-        Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[0]);
+        Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[kTmFftSyncMs]);
         ctx.run_fft_sync(nseg, samples, maxdrift, true, d_seglist, nact, nullptr, nullptr);
         ctx.fetch_candidates_async(nseg);
         t.stop();                                   // the one host wait of the pass start
@@ -491,8 +500,8 @@ std::vector<WaveItem> Context::DecodeRun::build_wave(const std::vector<int>& act
         for (int j = lo; j < hi; ++j) wave.push_back(WaveItem{s, j});
         if (!lockstep) next_cand[s] = n;
     }
-    c.t_ms[10] += (double)wave.size();
-    if (!wave.empty()) c.t_ms[11] += 1;
+    c.t_ms[kTmCandidatesRefined] += (double)wave.size();
+    if (!wave.empty()) c.t_ms[kTmGpuWaves] += 1;
     return wave;
 }
 
@@ -533,7 +542,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
     const float* wi = c.iqI.as<float>();
     const float* wq = c.iqQ.as<float>();
     {
-        Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[3]);
+        Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[kTmDemodMs]);
         upload(d_items, h_items, (size_t)nw * sizeof(FineState), c.stream);
         upload(d_lists, h_lists, (size_t)nw * 2 * 4, c.stream);
         // mode 0: lag scan (tiled), mode 1: 5 frequencies, mode 2: first rung of the ladder
@@ -577,7 +586,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
             if (!worth) continue;
             t.sync0 = h_sync[i]; t.rms0 = h_rms[i];
             memcpy(t.sym0, h_sym + (size_t)i * kNSymD, kNSymD);
-            t.fano_calls = (h_sync[i] > minsync2 && h_rms[i] > minrms) ? 1 : 0;
+            t.fano_calls = gated(i) ? 1 : 0;
         }
     // ---- first rung of the jitter ladder -----------------------------------
     const auto t_f0 = std::chrono::steady_clock::now();
@@ -591,7 +600,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
             w.decoded = false;
             w.jitter = 0;
             w.rung0_pending = false;
-            if (w.worth && h_sync[i] > minsync2 && h_rms[i] > minrms) att.push_back(i);
+            if (w.worth && gated(i)) att.push_back(i);
         }
         const int na = (int)att.size();
         std::vector<int> ret(na);
@@ -600,13 +609,10 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
         ctx.fano_resident(d_sym0, att.data(), na, 10000u, ret.data(), cyc.data(), dat.data());
         for (int k = 0; k < na; ++k) {
             WaveItem& w = wave[att[k]];
-            w.decoded = ret[k] == 0;
-            w.cycles = cyc[k];
-            memset(w.decdata, 0, sizeof w.decdata);
-            memcpy(w.decdata, dat.data() + (size_t)k * 10, 10);
+            take_device_result(w, ret[k] == 0, cyc[k], dat.data() + (size_t)k * 10);
             c.n_fano++; c.n_cycles += cyc[k]; if (ret[k]) c.n_timeout++;
         }
-        c.t_ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f0).count();
+        c.t_ms[kTmDeviceFanoTailMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f0).count();
         return;
     }
     // a candidate that passes the gates but does not decode costs a full time-out here
@@ -619,14 +625,14 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
         w.decoded = false;
         w.jitter = 0;
         if (!w.worth) return;
-        if (h_sync[i] > minsync2 && h_rms[i] > minrms) {
+        if (gated(i)) {
             const int nd = fano_attempt(h_sym + (size_t)i * kNSymD, &w.cycles, w.decdata);
             w.decoded = (nd == 0);
             w.rung0_pending = (nd != 0) && fast;
             if (!w.rung0_pending) { c.n_fano++; c.n_cycles += w.cycles; if (nd) c.n_timeout++; }
         }
     }, nw >= 256 ? 1 : 0);
-    c.t_ms[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f0).count();
+    c.t_ms[kTmHostFanoMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f0).count();
 
     if (fast)
         for (int i = 0; i < nw; ++i)
@@ -649,9 +655,8 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
         const size_t ntabs2 = plan_tables(h2, na, h_lists, &n_shared, &n_own);
         d_tabs = static_cast<float*>(c.tabs.need(ntabs2 * 2048 * 4));
         {
-            // all 43 lags shift-63 .. shift+63 in steps of 3 (rung r of the ladder = lag index
-            // (jitter+63)/3; index 21 repeats rung 0 and is ignored)
-            Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[3]);
+            // all 43 lags shift-63 .. shift+63 in steps of 3 (ladder_lag(); index 21 repeats rung 0 and is ignored)
+            Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[kTmDemodMs]);
             upload(d_items, h2, (size_t)na * sizeof(FineState), c.stream);
             upload(d_lists, h_lists, (size_t)na * 2 * 4, c.stream);
             launch_phasor_tables(d_items, na, 2, d_tabs, c.stream, call_arith());
@@ -677,8 +682,8 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
             ItemTrace& t = wtrace[again[a]];
             t.attempts = 1 + (lastr + 1);
             for (int r = 0; r <= lastr; ++r) {
-                const int g = a * kMaxLags + (c.jitter_ladder[r + 1] + 63) / 3;
-                if (h_sync[g] > minsync2 && h_rms[g] > minrms) t.fano_calls++;
+                const int g = a * kMaxLags + ladder_lag(r);
+                if (gated(g)) t.fano_calls++;
             }
         };
         if (c.dev_fano) {
@@ -689,8 +694,8 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
             std::vector<int> off, who;
             for (int a = 0; a < na; ++a)
                 for (int r = 0; r < njit_rest; ++r) {
-                    const int g = a * kMaxLags + (c.jitter_ladder[r + 1] + 63) / 3;
-                    if (h_sync[g] > minsync2 && h_rms[g] > minrms) { off.push_back(g); who.push_back(a * njit_rest + r); }
+                    const int g = a * kMaxLags + ladder_lag(r);
+                    if (gated(g)) { off.push_back(g); who.push_back(a * njit_rest + r); }
                 }
             const int nv = (int)off.size();
             std::vector<int> ret(nv);
@@ -707,13 +712,10 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
                 trace_ladder(a, at[a] >= 0 ? first[a] : njit_rest - 1);
                 if (at[a] < 0) continue;
                 WaveItem& w = wave[again[a]];
-                w.decoded = true;
                 w.jitter = c.jitter_ladder[first[a] + 1];
-                w.cycles = cyc[at[a]];
-                memset(w.decdata, 0, sizeof w.decdata);
-                memcpy(w.decdata, dat.data() + (size_t)at[a] * 10, 10);
+                take_device_result(w, true, cyc[at[a]], dat.data() + (size_t)at[a] * 10);
             }
-            c.t_ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_d0).count();
+            c.t_ms[kTmDeviceFanoTailMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_d0).count();
             return;
         }
         const auto t_f1 = std::chrono::steady_clock::now();
@@ -734,8 +736,8 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
             at.ok = 0;
             at.pending = 0;
             if (r > first[a].load()) return;           // an earlier rung already decoded
-            const size_t g = (size_t)a * kMaxLags + (size_t)((c.jitter_ladder[r + 1] + 63) / 3);
-            if (!(h_sync[g] > minsync2 && h_rms[g] > minrms)) return;
+            const size_t g = (size_t)a * kMaxLags + (size_t)ladder_lag(r);
+            if (!gated(g)) return;
             const int nd = fano_attempt(h_sym + g * kNSymD, &at.cycles, at.data);
             at.pending = (nd != 0) && fast;
             if (!at.pending) { c.n_fano++; c.n_cycles += at.cycles; if (nd) c.n_timeout++; }
@@ -750,7 +752,7 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
                 const int rmax = std::min(first[a].load(), njit_rest);
                 for (int r = 0; r < rmax; ++r)
                     if (att[(size_t)a * njit_rest + r].pending) {
-                        const size_t g = (size_t)a * kMaxLags + (size_t)((c.jitter_ladder[r + 1] + 63) / 3);
+                        const size_t g = (size_t)a * kMaxLags + (size_t)ladder_lag(r);
                         pend.add(wave[again[a]].seg, h_sym + g * kNSymD);
                     }
             }
@@ -765,7 +767,7 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
                 memcpy(w.decdata, att[(size_t)a * njit_rest + r].data, 11);
             }
         }
-        c.t_ms[5] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f1).count();
+        c.t_ms[kTmHostFanoMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f1).count();
     }
 }
 
@@ -878,7 +880,7 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
     std::vector<SubJob> jobs;
     for (int i = 0; i < nw; ++i) if (has_job[i]) jobs.push_back(job_of[i]);
     c.n_subjobs += (long)jobs.size();
-    c.t_ms[1] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_b0).count();
+    c.t_ms[kTmHostBookkeepingMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_b0).count();
     return jobs;
 }
 
@@ -902,7 +904,7 @@ void Context::DecodeRun::subtract(const std::vector<SubJob>& jobs) {
     launch_subtract(c.iqI.as<float>(), c.iqQ.as<float>(), samples, dj, nj, scratch, c.tab, c.stream, call_arith());
     if (slot_ev >= 0) {
         HIP_OK(hipEventRecord(c.ev_def[slot_ev][1], c.stream));
-        c.def_acc[slot_ev] = &c.t_ms[4];
+        c.def_acc[slot_ev] = &c.t_ms[kTmSubtractMs];
         c.n_def = slot_ev + 1;
     }
     HIP_OK(hipGetLastError());
@@ -963,25 +965,26 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
             active.swap(keep);
         }
         if (active.empty()) break;
-        { CpuSpan sp(&d->t_ms[17]); run.start_pass(ipass, active); }
+        { CpuSpan sp(&d->t_ms[kTmCpuMsPassStart]); run.start_pass(ipass, active); }
         for (;;) {
             std::vector<WaveItem> wave;
-            { CpuSpan sp(&d->t_ms[18]); wave = run.build_wave(active); }
+            { CpuSpan sp(&d->t_ms[kTmCpuMsBuildWave]); wave = run.build_wave(active); }
             if (wave.empty()) break;
-            { CpuSpan sp(&d->t_ms[19]); run.refine_and_first_rung(wave); }
-            { CpuSpan sp(&d->t_ms[20]); run.remaining_rungs(wave); }
+            { CpuSpan sp(&d->t_ms[kTmCpuMsRefine]); run.refine_and_first_rung(wave); }
+            { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.remaining_rungs(wave); }
             std::vector<SubJob> jobs;
-            { CpuSpan sp(&d->t_ms[21]); jobs = run.keep_books(wave); }
-            { CpuSpan sp(&d->t_ms[22]); run.subtract(jobs); }
+            { CpuSpan sp(&d->t_ms[kTmCpuMsBooks]); jobs = run.keep_books(wave); }
+            { CpuSpan sp(&d->t_ms[kTmCpuMsSubtract]); run.subtract(jobs); }
         }
     }
-    { CpuSpan sp(&d->t_ms[23]); run.finish(active0, n_results); }
+    { CpuSpan sp(&d->t_ms[kTmCpuMsFinish]); run.finish(active0, n_results); }
     guard.armed = false;
     return 0;
 }
 
 int Context::last_timings(double* ms, int cap) {
-    const int n = std::min(cap, 26);
+    static_assert(sizeof(Impl::t_ms) == kTimingSlots * sizeof(double), "one value per TimingSlot");
+    const int n = std::min(cap, (int)kTimingSlots);
     for (int i = 0; i < n; ++i) ms[i] = d->t_ms[i];
     return n;
 }

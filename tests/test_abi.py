@@ -82,6 +82,21 @@ def test_set_device_rejects_devices_that_do_not_exist():
         assert L.wspr_set_device(0) == 0
 
 
+def test_timing_names_cover_exactly_what_the_library_reports():
+    """wspr_last_timings() writes min(capacity, its own count) values; the wrapper's TIMING_NAMES must name every one of
+    them, in the order the public header documents ([0] .. [25]).  Needs no device: without a context the values are 0."""
+    L = w.lib()
+    ms = (C.c_double * 64)(*([-1.0] * 64))
+    n = L.wspr_last_timings(C.addressof(ms), 64)
+    assert n == len(w.TIMING_NAMES) == len(set(w.TIMING_NAMES))
+    assert all(v >= 0.0 for v in ms[:n]) and all(v == -1.0 for v in ms[n:])      # nothing written past the count
+    assert L.wspr_last_timings(C.addressof(ms), 3) == 3
+    hdr = open(os.path.join(ROOT, "include", "wspr_mi355x.h")).read()
+    doc = hdr[hdr.index("Timing of the stages of the most recent batch call"):hdr.index("int wspr_last_timings(")]
+    assert sorted(set(int(i) for i in re.findall(r"\[(\d+)\]", doc))) == list(range(n))
+    assert list(w.last_timings()) == list(w.TIMING_NAMES)
+
+
 def test_struct_layouts_match_reference():
     assert C.sizeof(w.decoder_options) == 40 and C.alignment(w.decoder_options) == 4
     assert [getattr(w.decoder_options, f).offset for f in

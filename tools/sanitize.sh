@@ -22,8 +22,7 @@ if [ "$cmd" = build ]; then
   FLAGS="--offload-arch=gfx950 -O2 -gline-tables-only -std=c++17 -fPIC -ffp-contract=off -fno-fast-math -fno-omit-frame-pointer -DWSPR_LAB -w"
   src="$root/rtlsdr-wsprd_amd/csrc"
   pids=()
-  for s in kernels/k0_decimate.hip kernels/k1_fft_bank.hip kernels/k2_k3_sync.hip kernels/k4_demod.hip kernels/k6_fano_wave.hip \
-           kernels/k7_subtract.hip host/wspr_context.hip host/wspr_pipeline.hip host/wspr_capi.hip; do
+  for s in $(cd "$src" && echo kernels/*.hip host/*.hip); do      # the set csrc/build.sh compiles
     $HIPCC $FLAGS $SAN -x hip -c "$src/$s" -o "$out/$(basename "${s%.*}").o" & pids+=($!)
   done
   for s in wspr_message wspr_hashmem; do
