@@ -227,6 +227,59 @@ size_t wspr_iq_stride(void);        /* floats per segment row of device IQ buffe
  * rtlsdr_wsprd.c:142-152) and the input samples per output (DOWNSAMPLING + 1 = 6401, :41, :198-202). */
 void wspr_front_end_constants(float *taps33, int *samples_per_output);
 
+/* ---- signal synthesiser (K8) ------------------------------------------------------------------------------
+ * The reference's self-test generator (decoderSelfTest() / whiteGaussianNoise(), rtlsdr_wsprd.c:706-760) for batches
+ * of scenes resident in HBM: from "symbols, frequency, time, level" to the IQ rows wspr_decode_batch_device() takes,
+ * reproducible sample for sample by a CPU (tests/helpers/synth_check.cpp is the contract in serial C).
+ *
+ * Per output sample x of a rail, in this order:
+ *   1. x = 0, or the row's present value with WSPR_SYNTH_ACCUMULATE.
+ *   2. If noise_sigma > 0: x = (float)((double)x + (double)n), n a float32 N(0, noise_sigma^2) draw that is a pure
+ *      function of (seed, seg_index0 + seg, sample index, rail): Philox-4x32-10 keyed by the seed, counter = (sample,
+ *      0, segment), Box-Muller with I = r cos(theta), Q = r sin(theta).  No state is carried between samples, so a
+ *      segment's noise does not depend on how a job is split into calls, batches or ranks.
+ *   3. For each transmission of that segment IN LIST ORDER: x = (float)((double)x + (double)amp * cos(phi)) (I rail;
+ *      sin for Q) -- for one transmission over zero or over a float noise sample the reference's statement :756-757.
+ * phi is the reference's serial recurrence: phi = 0.0, then for symbol i, sample j: use phi, then phi += dphi_i, with
+ *   dphi_i = 2.0 * M_PI * dt * ((f0 + fd_i) + ((double)symbols[i] - 1.5) * df),  df = 375.0/256.0,  dt = 1/375.0,
+ *   fd_i = (drift/2.0) * ((double)i - 81.0) / 81.0      -- all double, in that order; drift == 0 is :753 exactly.
+ * The recurrence is run as written (41 472 dependent double adds per transmission), not replaced by a prefix sum.
+ * Output index = floor(t0/dt) (double, once per transmission) + 256*i + j; samples outside [0, 45000) are dropped, so
+ * a frame may hang off either end of the row (the reference's index, :755, has no such guard).
+ * sin/cos of phi are a fixed sequence of IEEE double operations without fused multiply-add (fdlibm's reduction and
+ * kernels, rtlsdr-wsprd_amd/csrc/kernels/synth_math.h), the same on the device and on a CPU: they are WITHIN ONE
+ * DOUBLE ULP OF glibc's sin/cos, NOT glibc's -- about 3 % of the double values differ in the last bit; no float32
+ * sample of the scenes of tests/test_synth_checker.py does.  wspr_set_arithmetic() does not touch the synthesiser. */
+typedef struct wspr_synth_tx {      /* one transmission of a scene, 184 bytes */
+    int32_t seg;                    /* output row, 0 .. nseg-1; the list is sorted by seg (non-decreasing) */
+    float   f0;                     /* Hz from band centre, centre of the four tones (rtlsdr_wsprd.c:743) */
+    float   t0;                     /* s, start of symbol 0 (:744) */
+    float   amp;                    /* linear amplitude (:745) */
+    float   drift;                  /* Hz over the transmission, the decoder's own model (wsprd.c:156, 343); 0 = the reference generator */
+    unsigned char symbols[162];     /* channel symbols 0..3, e.g. from get_wspr_channel_symbols() */
+    unsigned char pad[2];
+} wspr_synth_tx;
+#define WSPR_SYNTH_ACCUMULATE 1     /* add to what the rows hold instead of starting from zero */
+#define WSPR_SYNTH_NORMALISE  2     /* afterwards the receiver's scaling to a peak of 0.5 (rtlsdr_wsprd.c:290-305) */
+/* d_idat / d_qdat: nseg device rows of wspr_iq_stride() floats, 16-byte aligned, exactly what
+ * wspr_decode_batch_device() takes (stream contract above: complete on return).  Without WSPR_SYNTH_ACCUMULATE the whole
+ * row is written (columns from 45000 on are zero); with it those columns are left alone.  Returns 0; -1 with a line on
+ * stderr and NOTHING WRITTEN for: no device, a symbol > 3, seg outside the batch, an unsorted list, negative counts, a
+ * non-finite f0 / t0 / amp / drift / noise_sigma, an unknown flag bit, misaligned rows, or |f0| + |drift|/2 > 1000 Hz
+ * (the range of the phase reduction; the band is +-187.5 Hz wide).  Takes a turn on the calling thread's lane; its
+ * scratch (the list, 5 184 B of phase checkpoints per transmission) belongs to the lane's context and is returned by
+ * wspr_release_buffers(). */
+int wspr_synth_batch_device(const wspr_synth_tx *tx, int ntx, int nseg, int seg_index0,
+                            float noise_sigma, uint64_t seed, int flags, void *d_idat, void *d_qdat);
+/* One segment into host rows of 45000 floats (read first with WSPR_SYNTH_ACCUMULATE), seg_index0 = 0: row 0 of the
+ * batch call. */
+int wspr_synth(const wspr_synth_tx *tx, int ntx, float noise_sigma, uint64_t seed, int flags,
+               float *I, float *Q);
+/* The reference's `-t` as one call (decoderSelfTest(), rtlsdr_wsprd.c:729-789): "K1JT FN20QI 20" at 50 Hz, 2.0 s,
+ * amplitude 1, noise 0.02 (seed 1), generated and decoded on the device.  Returns 1 / 0 by the rule of :782-788
+ * (negative: no usable device) and hands back the first spot (first may be NULL). */
+int wspr_selftest(struct decoder_options options, struct decoder_results *first);
+
 /* ---- receiver session --------------------------------------------------------------------
  * The reference's rx_state (two I/Q buffers of 45000 samples, their fill counters, the active index,
  * rtlsdr_wsprd.c:78-90), the decimator's static state (:135-160) and the body of its decoder thread (:263-328) as

@@ -45,6 +45,18 @@ class cand(C.Structure):                     # wsprd/wsprd.h:54-60
                 ("drift", C.c_float), ("sync", C.c_float)]
 
 
+class wspr_synth_tx(C.Structure):            # include/wspr_mi355x.h: one transmission of a synthesised scene
+    _fields_ = [("seg", C.c_int32), ("f0", C.c_float), ("t0", C.c_float), ("amp", C.c_float), ("drift", C.c_float),
+                ("symbols", C.c_ubyte * 162), ("pad", C.c_ubyte * 2)]
+
+
+# the same layout for numpy: a scene as one structured array (np.zeros(n, SYNTH_TX_DTYPE), fields filled columnwise)
+SYNTH_TX_DTYPE = np.dtype([("seg", "<i4"), ("f0", "<f4"), ("t0", "<f4"), ("amp", "<f4"), ("drift", "<f4"),
+                           ("symbols", "u1", (162,)), ("pad", "u1", (2,))])
+assert SYNTH_TX_DTYPE.itemsize == C.sizeof(wspr_synth_tx) == 184
+SYNTH_ACCUMULATE = 1
+SYNTH_NORMALISE = 2
+
 TRACE_PASSES = 3
 
 
@@ -110,6 +122,13 @@ def _bind(path):
     L.wspr_set_fano_fast_budget.restype = C.c_uint
     L.wspr_set_arithmetic.argtypes = [C.c_int]
     L.wspr_set_arithmetic.restype = C.c_int
+    L.wspr_synth_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int,
+                                          C.c_void_p, C.c_void_p]
+    L.wspr_synth_batch_device.restype = C.c_int
+    L.wspr_synth.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+    L.wspr_synth.restype = C.c_int
+    L.wspr_selftest.argtypes = [decoder_options, C.c_void_p]
+    L.wspr_selftest.restype = C.c_int
     L.nhash.restype = C.c_uint32
     L.nhash.argtypes = [C.c_char_p, C.c_size_t, C.c_uint32]
     L.pack_call.restype = C.c_ulong
@@ -182,6 +201,48 @@ def get_wspr_channel_symbols(message):
     sym = (C.c_ubyte * NSYM)()
     ok = lib().get_wspr_channel_symbols(C.create_string_buffer(message.encode(), 32), hashtab, loctab, sym)
     return int(ok), np.frombuffer(sym, dtype=np.uint8).copy()
+
+
+def synth_tx_list(items):
+    """[(seg, f0, t0, amp, drift, symbols[162]), ...] sorted by seg -> ctypes array of wspr_synth_tx."""
+    arr = (wspr_synth_tx * max(1, len(items)))()
+    for k, (seg, f0, t0, amp, drift, sym) in enumerate(items):
+        arr[k].seg, arr[k].f0, arr[k].t0, arr[k].amp, arr[k].drift = int(seg), f0, t0, amp, drift
+        arr[k].symbols[:] = [int(v) for v in sym]
+    return arr
+
+
+def wspr_synth_batch_device(items, nseg, d_i, d_q, seg_index0=0, noise_sigma=0.0, seed=0, flags=0):
+    """wspr_synth_batch_device() of include/wspr_mi355x.h: the scene `items` (a list as for synth_tx_list(), or a numpy
+    array of SYNTH_TX_DTYPE) into nseg device rows of wspr_iq_stride() floats at the raw pointers d_i / d_q.
+    Returns the library's code (0, or -1 with nothing written)."""
+    if isinstance(items, np.ndarray):
+        assert items.dtype == SYNTH_TX_DTYPE and items.flags.c_contiguous
+        tx, n = items.ctypes.data, int(items.size)
+    else:
+        arr = synth_tx_list(items)
+        tx, n = C.addressof(arr), len(items)
+    return lib().wspr_synth_batch_device(tx, n, nseg, seg_index0, noise_sigma, seed, flags, d_i, d_q)
+
+
+def wspr_synth(items, noise_sigma=0.0, seed=0, flags=0, I=None, Q=None):
+    """wspr_synth(): one segment into host rows of 45000 floats (given rows are copied and matter with SYNTH_ACCUMULATE).
+    Returns (I, Q); raises if the library refuses the call."""
+    I = np.zeros(NSAMPLES, np.float32) if I is None else np.array(I, np.float32).copy()
+    Q = np.zeros(NSAMPLES, np.float32) if Q is None else np.array(Q, np.float32).copy()
+    arr = synth_tx_list(items)
+    if lib().wspr_synth(C.addressof(arr), len(items), noise_sigma, seed, flags, _ptr(I), _ptr(Q)) != 0:
+        raise RuntimeError("wspr_synth failed (bad arguments, or no usable HIP device)")
+    return I, Q
+
+
+def wspr_selftest(options=None):
+    """The reference's `-t` (decoderSelfTest()) generated and decoded on the device: (1 / 0, first spot)."""
+    first = decoder_results()
+    rc = lib().wspr_selftest(options or default_options(), C.addressof(first))
+    if rc < 0:
+        raise RuntimeError("wspr_selftest failed (no usable HIP device?)")
+    return rc, first
 
 
 def wspr_decode(idat, qdat, samples=None, options=None):

@@ -164,6 +164,11 @@ public:
     int decimate_stream_many(DecimState* const* h_states, const uint8_t* const* iq, size_t nbytes, int n, float* const* I,
                              float* const* Q, const uint32_t* fill, uint32_t cap, uint32_t* new_fill);
 
+    // K8 (wspr_capi_synth.hip): a validated, sorted transmission list into nseg device rows; complete on return
+    int synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, float sigma, uint64_t seed,
+                     int flags, float* dI, float* dQ);
+    float* synth_rows();            // two rows of kIqStride floats of the context's own (wspr_selftest)
+
     struct Impl;
     struct DecodeRun;               // state of one decode_core() call (wspr_pipeline.hip)
     std::unique_ptr<Impl> d;

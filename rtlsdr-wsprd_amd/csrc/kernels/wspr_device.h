@@ -168,6 +168,19 @@ size_t fano_wave_scratch_words(int n);
 void launch_fano_wave(const unsigned char* symbols, const int* offsets, int n, const short* metric0,
                       unsigned maxcycles, int* ret, unsigned* cycles, unsigned* metric, unsigned* maxnp,
                       unsigned char* data, unsigned* steps, uint32_t* scratch, hipStream_t st);
+// K8, the signal synthesiser (k8_synth.hip; arithmetic in synth_math.h).  SynthTx is wspr_synth_tx of the public header.
+struct SynthTx {
+    int32_t seg;
+    float f0, t0, amp, drift;
+    unsigned char symbols[kNSymD];
+    unsigned char pad[2];
+};
+size_t synth_checkpoint_doubles(int ntx);                 // phase checkpoints of ntx transmissions
+// tx sorted by seg, seg_off[nseg + 1] its offsets per segment (both device memory); ckpt: synth_checkpoint_doubles(ntx)
+// doubles, first: ntx ints of scratch.  Rows of kIqStride floats, 16-byte aligned; without `accumulate` the whole row is
+// written (columns >= 45000 zero), with it those columns are left alone.
+void launch_synth(const SynthTx* tx, int ntx, const int* seg_off, int nseg, long long seg_index0, float sigma,
+                  unsigned long long seed, int accumulate, double* ckpt, int* first, float* dI, float* dQ, hipStream_t st);
 void launch_normalise(float* dI, float* dQ, const int* n_valid, int nseg, int n_total, hipStream_t st);
 // resident input rows -> working rows (zero tail); false if the input is not 16-byte friendly
 bool launch_load_rows(const float* sI, const float* sQ, size_t stride, int samples, int nseg, float* dI, float* dQ,
