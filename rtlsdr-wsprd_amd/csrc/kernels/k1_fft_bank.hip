@@ -29,6 +29,7 @@
 // The butterfly arithmetic (u+v, (u-v)*w with separately rounded products) is the
 // same as the CPU oracle's orc_fft512(), so results are bit-identical to it.
 #include "wspr_device.h"
+#include "arith.h"
 #include <cstdlib>
 
 #pragma clang fp contract(off)
@@ -151,9 +152,20 @@ static_assert(out_rows_share_a_skew(), "every kOutRow[r] is 16 mod 64: one skew 
 // One FFT of the run: window, 3 passes, power into the workgroup's output tile.  `raw` is the sliding
 // window of raw samples, raw[(base + r) & 7] = row r of this block; rotating `base` by 2 per block
 // instead of moving registers needs the run loop unrolled by 4 (kBase is a compile-time constant).
-// The powers of wsprd.c:551, re*re + im*im: kFma (wspr_set_arithmetic, contracted mode) fuses them as clang's
-// -ffp-contract=on does, fma(re, re, im*im); otherwise two separately rounded products and their sum.
-__device__ __forceinline__ float power_fma(const v2 x) { return __builtin_fmaf(x.x, x.x, x.y * x.y); }
+// The powers of wsprd.c:551, re*re + im*im, go through Arith<kFma> (arith.h; kFma: wspr_set_arithmetic).
+// x[r] holds bin rev9(8*lane + r) = 64*rev3(r) + rev6(lane); see OutCols for its row in the output tile `ob`
+template <bool kFma, int kPitch>
+__device__ __forceinline__ void store_powers(const v2 (&x)[8], float* __restrict__ ob, const OutCols ocol) {
+    float pw[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) pw[r] = Arith<kFma>::mma(x[r].x, x[r].x, x[r].y, x[r].y);
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        if (r == 1)      ob[ocol.at1] = pw[r];
+        else if (r == 6) ob[ocol.at6] = pw[r];
+        else ob[ocol.base + kOutRow[r] * kPitch] = pw[r];
+    }
+}
 
 template <bool kFma, int kBase, int kPitch, bool kBarrierBeforeWrite = false, bool kRefill = false>
 __device__ __forceinline__ void one_fft(v2 (&raw)[8], const float (&win)[8], const Tw& twA, const Tw& twB, float w8,
@@ -196,19 +208,8 @@ __device__ __forceinline__ void one_fft(v2 (&raw)[8], const float (&win)[8], con
 
     pass3_last(x, w8);
 
-    // x[r] now holds bin rev9(8*lane + r) = 64*rev3(r) + rev6(lane); see OutCols for its row in the output tile
     if (kBarrierBeforeWrite) __syncthreads();       // fused kernel: the previous group's tile has been consumed
-    float* __restrict__ ob = otile + tl;                            // 64 lanes -> 64 different bins: 2 lanes per bank
-    v2 e[8];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) e[r] = x[r] * x[r];
-#pragma unroll
-    for (int r = 0; r < 8; ++r) {
-        const float pw = kFma ? power_fma(x[r]) : e[r].x + e[r].y;
-        if (r == 1)      ob[ocol.at1] = pw;
-        else if (r == 6) ob[ocol.at6] = pw;
-        else ob[ocol.base + kOutRow[r] * kPitch] = pw;
-    }
+    store_powers<kFma, kPitch>(x, otile + tl, ocol);                // 64 lanes -> 64 different bins: 2 lanes per bank
 }
 
 // Where register r's bin goes.  With lo = rev6(lane), x[r] is natural bin 64 rev3(r) + lo; fft-shifted (+256 mod 512)
@@ -366,32 +367,10 @@ __device__ __forceinline__ void fft_pair(v2 (&S)[10], const float (&win)[8], con
 
     pass3_last(xa, w8);
     if (kBarrierBeforeWrite) __syncthreads();       // the previous group's tile has been consumed
-    {
-        v2 e[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) e[r] = xa[r] * xa[r];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const float pw = kFma ? power_fma(xa[r]) : e[r].x + e[r].y;
-            if (r == 1)      obA[ocol.at1] = pw;
-            else if (r == 6) obA[ocol.at6] = pw;
-            else obA[ocol.base + kOutRow[r] * kPitch] = pw;
-        }
-    }
+    store_powers<kFma, kPitch>(xa, obA, ocol);
     __builtin_amdgcn_sched_barrier(0);
     pass3_last(xb, w8);
-    if (has_b) {                                     // wave-uniform
-        v2 e[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) e[r] = xb[r] * xb[r];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) {
-            const float pw = kFma ? power_fma(xb[r]) : e[r].x + e[r].y;
-            if (r == 1)      obB[ocol.at1] = pw;
-            else if (r == 6) obB[ocol.at6] = pw;
-            else obB[ocol.base + kOutRow[r] * kPitch] = pw;
-        }
-    }
+    if (has_b) store_powers<kFma, kPitch>(xb, obB, ocol);           // wave-uniform
 }
 
 // Fused form for large batches: ONE workgroup walks a whole segment, 16 time blocks (4 per wave) at a

@@ -22,8 +22,10 @@
 //   mode 1 + rung 0, drift      freq_drift_kernel + freq_metric_kernel
 //   epilogues             pick_lag_kernel, pick_freq_kernel;  calibration: calib_valu_kernel
 #include "wspr_device.h"
+#include "arith.h"
 #include "glibc_sincosf.h"
 #include <cstdlib>
+#include <type_traits>
 
 #pragma clang fp contract(off)
 
@@ -34,13 +36,87 @@ constexpr double kTwoPiDt = 2.0 * 3.14159265358979323846 * 1.0 / 375.0;   // TWO
 constexpr double kDf05 = 375.0 / 256.0 * 0.5;
 constexpr double kDf15 = 375.0 / 256.0 * 1.5;
 
-// Arithmetic policy (wspr_set_arithmetic): every kernel that evaluates a contraction site of wsprd.c is a template on
-// kFma.  kFma = false is the exact mode: separately rounded multiplies and adds, the source as it always was.
-// kFma = true is the contracted mode: each site as clang's -ffp-contract=on fuses it in wsprd.c, the LEFT product of a
-// sum into the fma (a*b + c*d -> fma(a, b, c*d), (acc + x*c) + y*s -> fma(y, s, fma(x, c, acc)), acc - x*s ->
-// fma(-x, s, acc)); per-lane accumulation order stays the reference's loop order.
-__device__ __forceinline__ float fmaf1(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
+// ---- the pieces every kernel of this file shares; each contraction site goes through Arith<kFma> (arith.h) ----------
 
+// f0 = *freq + ifreq * fstep, wsprd.c:151
+template <bool kFma>
+__device__ __forceinline__ float hyp_freq(float freq, int ifreq, float fstep) {
+    return Arith<kFma>::mad((float)ifreq, fstep, freq);
+}
+
+// Phase step of one tone of one symbol (wsprd.c:158-177): the symbol's frequency on the drift line, in float as the
+// reference keeps it, then the tone's offset in double.  f0 is the reference's float, widened (exactly) by the call.
+__device__ __forceinline__ float tone_dphi(double f0, float drift, int sym, int tone) {
+    const float fp = (float)(f0 + ((double)drift / 2.0) * (double)((float)sym - 81.0f) / (double)81.0f);
+    const double off = (tone == 0) ? -kDf15 : (tone == 1) ? -kDf05 : (tone == 2) ? kDf05 : kDf15;
+    return (float)(kTwoPiDt * ((double)fp + off));
+}
+
+// One step of the phasor recurrence (wsprd.c:180-187): c' = c*cd - s*sd, s' = c*sd + s*cd; T = float or v2f
+template <bool kFma, class T>
+__device__ __forceinline__ void phasor_step(T& c, T& s, T cd, T sd) {
+    const T cn = Arith<kFma>::mms(c, cd, s, sd);
+    s = Arith<kFma>::mma(c, sd, s, cd);
+    c = cn;
+}
+
+// One tone's table: 256 steps of the recurrence from (1, 0) into t[256][8] = (cos of tones 0..3, sin of tones 0..3)
+template <bool kFma>
+__device__ __forceinline__ void build_phasor_table(float dphi, int tone, float* __restrict__ t) {
+    const float cd = glibc_cosf(dphi), sd = glibc_sinf(dphi);
+    float c = 1.0f, s = 0.0f;
+    for (int j = 0; j < kSps; ++j) {
+        if (j > 0) phasor_step<kFma>(c, s, cd, sd);
+        t[8 * j + tone] = c;
+        t[8 * j + 4 + tone] = s;
+    }
+}
+
+// Sync metric of one hypothesis (wsprd.c:209-218): the 162 symbols' tone amplitudes amp(k) folded in symbol order
+template <class Amp>
+__device__ __forceinline__ float sync_metric(Amp amp, const unsigned char* __restrict__ pr3) {
+    float ss = 0.0f, totp = 0.0f;
+    for (int k = 0; k < kNSymD; ++k) {
+        const float4 p = amp(k);
+        totp = totp + p.x + p.y + p.z + p.w;
+        const float cmet = (p.y + p.w) - (p.x + p.z);
+        ss = pr3[k] ? ss + cmet : ss - cmet;
+    }
+    return ss / totp;
+}
+
+// Soft symbols, wsprd.c:219-225 and :243-256.  fsymb of one symbol from its amplitudes and its sync bit:
+__device__ __forceinline__ float soft_f(const float4 p, unsigned char sync_bit) { return sync_bit ? p.w - p.y : p.z - p.x; }
+// their mean and mean square, in symbol order, and the normalisation fac = sqrt(f2sum - fsum*fsum):
+struct SoftNorm {
+    float fsum = 0.0f, f2sum = 0.0f;
+    __device__ __forceinline__ void add(float f) {
+        fsum += f / 162.0f;
+        const float ff = f * f;
+        f2sum += ff / 162.0f;
+    }
+    template <bool kFma>
+    __device__ __forceinline__ float fac() const { return sqrtf(Arith<kFma>::nmad(fsum, fsum, f2sum)); }
+};
+// symfac * fsymb[i] / fac (wsprd.c:250, int -> float), clamped to -128 .. 127, offset by 128; NaN -> 0
+__device__ __forceinline__ unsigned char soft_quantise(float f, float fac, float symfac) {
+    float v = symfac * f / fac;
+    if (v > 127.0f) v = 127.0f;
+    if (v < -128.0f) v = -128.0f;
+    const float w = v + 128.0f;
+    return (w == w) ? (unsigned char)(int)w : (unsigned char)0;
+}
+// a quantised symbol's term of the rms (a small integer squared: the sum is exact in any order)
+__device__ __forceinline__ float soft_square(unsigned char b) {
+    const float y = (float)b - 128.0f;
+    return y * y;
+}
+constexpr float kSymFac = 50.0f;      // the symfac of every caller but the exported sync_and_demodulate()
+
+// Staging of the three lane = symbol kernels (demod_kernel, freq_scalar_kernel, freq_drift_kernel: fetch the next chunk
+// into registers, commit it to tile[162][32 + 1]) is written out in each of them: moved into a shared function the
+// compiler re-derives the index arithmetic of the whole kernel (freq_scalar_kernel: 52 -> 50 VGPRs, another
+// instruction mix), and those kernels are kept instruction for instruction (tools/kernel_isa_diff.py).
 constexpr int kGenThreads = 192;
 constexpr int kGenChunk = 32;
 constexpr int kGenPerThread = kNSymD * kGenChunk / kGenThreads;     // 27 samples staged per thread and chunk
@@ -53,6 +129,7 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
                   int nlag, int lagstep, int ifmin, float fstep, const int* __restrict__ jitter,
                   float minsync1, float* __restrict__ sync_out, unsigned char* __restrict__ sym_out,
                   float* __restrict__ rms_out, const unsigned char* __restrict__ pr3, float symfac) {
+    using A = Arith<kFma>;
     __shared__ float pw[kNSymD][4];
     __shared__ float2 tile[kNSymD][kGenChunk + 1];
     const int item = item_list ? item_list[blockIdx.y] : (int)blockIdx.y, hyp = blockIdx.x;
@@ -64,8 +141,7 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
         f0 = st.freq_coarse;
         lag = st.shift_coarse - 128 + lagstep * hyp;
     } else if (mode == 1) {
-        if constexpr (kFma) f0 = fmaf1((float)(ifmin + hyp), fstep, st.freq);
-        else f0 = st.freq + (float)(ifmin + hyp) * fstep;      // *freq + ifreq * fstep, wsprd.c:151
+        f0 = hyp_freq<kFma>(st.freq, ifmin + hyp, fstep);
         lag = st.shift;
     } else {
         if (!(st.sync > minsync1)) return;              // not worth a try (wsprd.c:733-737)
@@ -73,23 +149,18 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
         lag = st.shift + jitter[hyp];
     }
 
-    // lane = symbol.  The samples stream through LDS in chunks of 32 per symbol (coalesced 128-byte row
-    // segments from HBM/L2, transposed so that lane = symbol reads conflict-free), the next chunk in flight
-    // in registers while the current one is consumed; the four tone phasors are the reference's float
+    // lane = symbol; the samples come through the chunk stager; the four tone phasors are the reference's float
     // recurrences, run inline.
     const int i = threadIdx.x, tid = threadIdx.x;
     const float* __restrict__ xi = dI + (size_t)st.seg * kIqStride;
     const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
     float cd[4], sd[4], c[4], s[4], ai[4], aq[4];
     if (i < kNSymD) {
-        const float fp = (float)((double)f0 + ((double)st.drift / 2.0) * (double)((float)i - 81.0f) / (double)81.0f);
-        const double fpd = (double)fp;
-        const float dphi[4] = {(float)(kTwoPiDt * (fpd - kDf15)), (float)(kTwoPiDt * (fpd - kDf05)),
-                               (float)(kTwoPiDt * (fpd + kDf05)), (float)(kTwoPiDt * (fpd + kDf15))};
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
-            cd[t] = glibc_cosf(dphi[t]);
-            sd[t] = glibc_sinf(dphi[t]);
+            const float dphi = tone_dphi(f0, st.drift, i, t);
+            cd[t] = glibc_cosf(dphi);
+            sd[t] = glibc_sinf(dphi);
             c[t] = 1.0f; s[t] = 0.0f; ai[t] = 0.0f; aq[t] = 0.0f;
         }
     }
@@ -120,32 +191,14 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
                 const int k = base + jj;
                 if (kGenChunk * ch + jj > 0) {
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        if constexpr (kFma) {
-                            const float cn = fmaf1(c[t], cd[t], -(s[t] * sd[t]));
-                            s[t] = fmaf1(c[t], sd[t], s[t] * cd[t]);
-                            c[t] = cn;
-                        } else {
-                        const float a = c[t] * cd[t], b = s[t] * sd[t];
-                        const float e = c[t] * sd[t], d = s[t] * cd[t];
-                        c[t] = a - b;
-                        s[t] = e + d;
-                        }
-                    }
+                    for (int t = 0; t < 4; ++t) phasor_step<kFma>(c[t], s[t], cd[t], sd[t]);
                 }
                 if (k > 0 && k < np) {
                     const float2 xy = tile[i][jj];
 #pragma unroll
-                    for (int t = 0; t < 4; ++t) {
-                        if constexpr (kFma) {
-                            ai[t] = fmaf1(xy.y, s[t], fmaf1(xy.x, c[t], ai[t]));
-                            aq[t] = fmaf1(xy.y, c[t], fmaf1(-xy.x, s[t], aq[t]));
-                        } else {
-                        const float m1 = xy.x * c[t], m2 = xy.y * s[t];
-                        const float m3 = xy.x * s[t], m4 = xy.y * c[t];
-                        ai[t] = (ai[t] + m1) + m2;
-                        aq[t] = (aq[t] - m3) + m4;
-                        }
+                    for (int t = 0; t < 4; ++t) {       // ai = (ai + x*c) + y*s ; aq = (aq - x*s) + y*c (wsprd.c:200-207)
+                        ai[t] = A::mad(xy.y, s[t], A::mad(xy.x, c[t], ai[t]));
+                        aq[t] = A::mad(xy.y, c[t], A::nmad(xy.x, s[t], aq[t]));
                     }
                 }
             }
@@ -153,58 +206,27 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
     }
     if (i < kNSymD) {
 #pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if constexpr (kFma) {
-                pw[i][t] = sqrtf(fmaf1(ai[t], ai[t], aq[t] * aq[t]));
-            } else {
-            const float e1 = ai[t] * ai[t], e2 = aq[t] * aq[t];
-            pw[i][t] = sqrtf(e1 + e2);
-            }
-        }
+        for (int t = 0; t < 4; ++t) pw[i][t] = sqrtf(A::mma(ai[t], ai[t], aq[t], aq[t]));
     }
     __syncthreads();
 
     if (threadIdx.x == 0) {
-        float ss = 0.0f, totp = 0.0f;
-        for (int k = 0; k < kNSymD; ++k) {
-            const float p0 = pw[k][0], p1 = pw[k][1], p2 = pw[k][2], p3 = pw[k][3];
-            totp = totp + p0 + p1 + p2 + p3;
-            const float cmet = (p1 + p3) - (p0 + p2);
-            ss = pr3[k] ? ss + cmet : ss - cmet;
-        }
-        ss = ss / totp;
+        auto amp = [&](int k) { return make_float4(pw[k][0], pw[k][1], pw[k][2], pw[k][3]); };
+        const float ss = sync_metric(amp, pr3);
         const size_t o = (size_t)item * nlag + hyp;
         if (mode != 2) {
             sync_out[o] = ss;
         } else {
             sync_out[o] = (ss > -1e30f) ? ss : -1e30f;
-            // soft symbols, wsprd.c:219-225 and :243-256
-            float fsum = 0.0f, f2sum = 0.0f;
-            for (int k = 0; k < kNSymD; ++k) {
-                const float f = pr3[k] ? pw[k][3] - pw[k][1] : pw[k][2] - pw[k][0];
-                fsum += f / 162.0f;
-                const float ff = f * f;
-                f2sum += ff / 162.0f;
-            }
-            float fac;
-            if constexpr (kFma) {
-                fac = sqrtf(fmaf1(-fsum, fsum, f2sum));
-            } else {
-            const float m2 = fsum * fsum;
-            fac = sqrtf(f2sum - m2);
-            }
+            SoftNorm norm;
+            for (int k = 0; k < kNSymD; ++k) norm.add(soft_f(amp(k), pr3[k]));
+            const float fac = norm.fac<kFma>();
             float sq = 0.0f;
             unsigned char* __restrict__ so = sym_out + o * kNSymD;
             for (int k = 0; k < kNSymD; ++k) {
-                const float f = pr3[k] ? pw[k][3] - pw[k][1] : pw[k][2] - pw[k][0];
-                float v = symfac * f / fac;                 // symfac * fsymb[i] / fac, wsprd.c:250 (int -> float)
-                if (v > 127.0f) v = 127.0f;
-                if (v < -128.0f) v = -128.0f;
-                const float w = v + 128.0f;
-                const unsigned char b = (w == w) ? (unsigned char)(int)w : (unsigned char)0;
+                const unsigned char b = soft_quantise(soft_f(amp(k), pr3[k]), fac, symfac);
                 so[k] = b;
-                const float y = (float)b - 128.0f;
-                sq += y * y;
+                sq += soft_square(b);
             }
             rms_out[o] = sqrtf(sq / 162.0f);
         }
@@ -229,62 +251,46 @@ void demod_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
 // Packed-pair arithmetic: gfx950 executes v_pk_mul_f32 / v_pk_add_f32 on register pairs; each
 // half is an ordinary IEEE multiply or add (no fusion), so the per-accumulator operation
 // sequence -- and therefore every bit -- is unchanged.  Tones (0,1) and (2,3) share a pair.
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-// Contracted mode (kFma): each site is one v_pk_fma_f32 on the pair, i.e. two IEEE fmas (wsprd.c:200-207 fuse as
-// fma(y, s, fma(x, c, ai)) and fma(y, c, fma(-x, s, aq)), wsprd.c:211-214 as fma(i, i, q*q)).
-__device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-
+// Contracted mode: each site is one v_pk_fma_f32 on the pair, i.e. two IEEE fmas.
 template <bool kFma>
 struct ToneAcc {
+    using A = Arith<kFma>;
     v2f i01, i23, q01, q23;
     __device__ __forceinline__ void clear() { i01 = i23 = q01 = q23 = (v2f){0.0f, 0.0f}; }
-    // contracted mode: one sample (x, y) on the four tones' pairs (c01, c23, s01, s23)
-    __device__ __forceinline__ void step_fma(const v2f xx, const v2f yy, const v2f c01, const v2f c23, const v2f s01,
-                                             const v2f s23) {
-        const v2f nx = -xx;
-        i01 = fma2(yy, s01, fma2(xx, c01, i01));
-        i23 = fma2(yy, s23, fma2(xx, c23, i23));
-        q01 = fma2(yy, c01, fma2(nx, s01, q01));
-        q23 = fma2(yy, c23, fma2(nx, s23, q23));
+    // one sample (x, y) on the four tones' pairs: ai = (ai + x*c) + y*s ; aq = (aq - x*s) + y*c   (wsprd.c:200-207)
+    __device__ __forceinline__ void step(const v2f xx, const v2f yy, const v2f c01, const v2f c23, const v2f s01,
+                                         const v2f s23) {
+        i01 = A::mad(yy, s01, A::mad(xx, c01, i01));
+        i23 = A::mad(yy, s23, A::mad(xx, c23, i23));
+        q01 = A::mad(yy, c01, A::nmad(xx, s01, q01));
+        q23 = A::mad(yy, c23, A::nmad(xx, s23, q23));
     }
-    // ai = (ai + x*c) + y*s ; aq = (aq - x*s) + y*c   (wsprd.c:200-207)
     __device__ __forceinline__ void step(const float2 d, const float4 c4, const float4 s4) {
-        const v2f xx = {d.x, d.x}, yy = {d.y, d.y};
-        const v2f c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w}, s01 = {s4.x, s4.y}, s23 = {s4.z, s4.w};
-        if constexpr (kFma) {
-            step_fma(xx, yy, c01, c23, s01, s23);
-        } else {
-        i01 = (i01 + xx * c01) + yy * s01;
-        i23 = (i23 + xx * c23) + yy * s23;
-        q01 = (q01 - xx * s01) + yy * c01;
-        q23 = (q23 - xx * s23) + yy * c23;
-        }
+        step((v2f){d.x, d.x}, (v2f){d.y, d.y}, (v2f){c4.x, c4.y}, (v2f){c4.z, c4.w}, (v2f){s4.x, s4.y}, (v2f){s4.z, s4.w});
     }
+    // The exact mode's step() in SPREAD form, for the hand-scheduled loops (lagsys_wave, demod_drift_kernel): the eight
+    // products of a sample are formed first and added afterwards, x's before y's as in step(), so that dependent packed
+    // instructions sit apart (folded into step() the two kernels stall: 59 -> 266 and 75 -> 147 s_nop).
+    struct Products { v2f xc01, xc23, xs01, xs23, ys01, ys23, yc01, yc23; };
+    static __device__ __forceinline__ Products products(const v2f xx, const v2f yy, const v2f c01, const v2f c23,
+                                                        const v2f s01, const v2f s23) {
+        static_assert(!kFma, "the contracted mode has no separate products: step()");
+        return {xx * c01, xx * c23, xx * s01, xx * s23, yy * s01, yy * s23, yy * c01, yy * c23};
+    }
+    __device__ __forceinline__ void add_x(const Products& p) {
+        i01 = i01 + p.xc01; i23 = i23 + p.xc23;
+        q01 = q01 - p.xs01; q23 = q23 - p.xs23;
+    }
+    __device__ __forceinline__ void add_y(const Products& p) {
+        i01 = i01 + p.ys01; i23 = i23 + p.ys23;
+        q01 = q01 + p.yc01; q23 = q23 + p.yc23;
+    }
+    // wsprd.c:211-214: sqrt(i*i + q*q) per tone
     __device__ __forceinline__ float4 amplitudes() const {
-        if constexpr (kFma) {
-            const v2f e01 = fma2(i01, i01, q01 * q01), e23 = fma2(i23, i23, q23 * q23);
-            return make_float4(sqrtf(e01.x), sqrtf(e01.y), sqrtf(e23.x), sqrtf(e23.y));
-        } else {
-        const v2f e01 = i01 * i01 + q01 * q01, e23 = i23 * i23 + q23 * q23;
+        const v2f e01 = A::mma(i01, i01, q01, q01), e23 = A::mma(i23, i23, q23, q23);
         return make_float4(sqrtf(e01.x), sqrtf(e01.y), sqrtf(e23.x), sqrtf(e23.y));
-        }
     }
 };
-
-// One step of the phasor recurrence (wsprd.c:180-187): c' = c*cd - s*sd, s' = c*sd + s*cd
-template <bool kFma>
-__device__ __forceinline__ void phasor_step(float& c, float& s, float cd, float sd) {
-    if constexpr (kFma) {
-        const float cn = fmaf1(c, cd, -(s * sd));
-        s = fmaf1(c, sd, s * cd);
-        c = cn;
-    } else {
-        const float a = c * cd, b = s * sd, e = c * sd, d = s * cd;
-        c = a - b;
-        s = e + d;
-    }
-}
 
 constexpr int kTileSymsShared = 9;    // 9 x 33 lags = 297 of 320 lanes; 28 KB of LDS
 constexpr int kTileSymsOwn = 6;       // per-symbol tables: 6 x 8 KB + tile
@@ -303,17 +309,7 @@ void phasor_table_kernel(const FineState* __restrict__ items, int mode, float* _
     // drifting candidates build their per-symbol tables inside demod_tile_kernel<., false>
     if (st.drift != 0.0f || sym != 0) return;
     const float f0 = (mode == 0) ? st.freq_coarse : st.freq;
-    const float fp = (float)((double)f0 + ((double)st.drift / 2.0) * (double)((float)sym - 81.0f) / (double)81.0f);
-    const double off = (tone == 0) ? -kDf15 : (tone == 1) ? -kDf05 : (tone == 2) ? kDf05 : kDf15;
-    const float dphi = (float)(kTwoPiDt * ((double)fp + off));
-    const float cd = glibc_cosf(dphi), sd = glibc_sinf(dphi);
-    float* __restrict__ t = tabs + (size_t)st.pad * 2048;   // [256][8]
-    float c = 1.0f, s = 0.0f;
-    for (int j = 0; j < kSps; ++j) {
-        if (j > 0) phasor_step<kFma>(c, s, cd, sd);
-        t[8 * j + tone] = c;
-        t[8 * j + 4 + tone] = s;
-    }
+    build_phasor_table<kFma>(tone_dphi(f0, st.drift, sym, tone), tone, tabs + (size_t)st.pad * 2048);   // [256][8]
 }
 
 template <int STEP, bool SHARED, bool kFma>
@@ -349,17 +345,8 @@ void demod_tile_kernel(const float* __restrict__ dI, const float* __restrict__ d
         if (tid < kTileSyms * 4) {
             const int il = tid >> 2, tone = tid & 3, sym = i0 + il;
             const float f0 = (mode == 0) ? st.freq_coarse : st.freq;
-            const float fp = (float)((double)f0 + ((double)st.drift / 2.0) * (double)((float)sym - 81.0f) / (double)81.0f);
-            const double off = (tone == 0) ? -kDf15 : (tone == 1) ? -kDf05 : (tone == 2) ? kDf05 : kDf15;
-            const float dphi = (float)(kTwoPiDt * ((double)fp + off));
-            const float cd = glibc_cosf(dphi), sd = glibc_sinf(dphi);
-            float* __restrict__ t = reinterpret_cast<float*>(tab + il * kOwnTabPitch);     // [256][8]
-            float c = 1.0f, s = 0.0f;
-            for (int j = 0; j < kSps; ++j) {
-                if (j > 0) phasor_step<kFma>(c, s, cd, sd);
-                t[8 * j + tone] = c;
-                t[8 * j + 4 + tone] = s;
-            }
+            build_phasor_table<kFma>(tone_dphi(f0, st.drift, sym, tone), tone,
+                                     reinterpret_cast<float*>(tab + il * kOwnTabPitch));     // [256][8]
         }
     }
     for (int e0 = tid; e0 < span; e0 += 4 * nthr) {
@@ -476,10 +463,7 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
     const bool builder = lane < kDrSyms * 4;
     float cd = 1.0f, sd = 0.0f, pc = 1.0f, ps = 0.0f;
     if (builder) {
-        const int sym = i0 + bil;
-        const float fp = (float)((double)st.freq_coarse + ((double)st.drift / 2.0) * (double)((float)sym - 81.0f) / (double)81.0f);
-        const double off = (tone == 0) ? -kDf15 : (tone == 1) ? -kDf05 : (tone == 2) ? kDf05 : kDf15;
-        const float dphi = (float)(kTwoPiDt * ((double)fp + off));
+        const float dphi = tone_dphi(st.freq_coarse, st.drift, i0 + bil, tone);
         cd = glibc_cosf(dphi);
         sd = glibc_sinf(dphi);
     }
@@ -496,15 +480,11 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
         __syncthreads();                                     // the previous 32 table steps have been consumed
         if (builder) {
             for (int jj = 0; jj < kDrChunk; ++jj) {
-                if (ch + jj > 0) {
-                    if constexpr (kFma) {
-                        phasor_step<true>(pc, ps, cd, sd);
-                    } else {
-                    const float a = pc * cd, b = ps * sd, e = pc * sd, d = ps * cd;
-                    pc = a - b;
-                    ps = e + d;
-                    }
-                }
+                // formed for every entry and taken from the second on (as a conditional call the exact build gains
+                // 20 register moves)
+                float nc = pc, ns = ps;
+                phasor_step<kFma>(nc, ns, cd, sd);
+                if (ch + jj > 0) { pc = nc; ps = ns; }
                 tabw[8 * jj] = pc;
                 tabw[8 * jj + 4] = ps;
             }
@@ -519,8 +499,7 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
                     const int e = e_lane + 8 * kDrGroups * r + kDrChunk * ch + jb;      // a multiple of 8
                     t0[r] = tile + (e >> 3) + kDrSkew * (e >> 8);
                 }
-                // operands of step u+1 are in flight while step u is consumed; the 24 products of a step are
-                // formed before the 24 accumulator updates, so dependent instructions sit far apart
+                // operands of step u+1 are in flight while step u is consumed
                 float4 c4 = tb[2 * jb], s4 = tb[2 * jb + 1];
                 float2 d[3];
 #pragma unroll
@@ -539,25 +518,17 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
                     if constexpr (kFma) {
 #pragma unroll
                         for (int r = 0; r < 3; ++r)
-                            acc[r].step_fma((v2f){d[r].x, d[r].x}, (v2f){d[r].y, d[r].y}, c01, c23, s01, s23);
+                            acc[r].step((v2f){d[r].x, d[r].x}, (v2f){d[r].y, d[r].y}, c01, c23, s01, s23);
                     } else {
-                    v2f p[3][8];
+                        // hand-scheduled (ToneAcc::products): the 24 products of a step, then the 24 accumulator updates
+                        typename ToneAcc<kFma>::Products p[3];
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        const v2f xx = {d[r].x, d[r].x}, yy = {d[r].y, d[r].y};
-                        p[r][0] = xx * c01; p[r][1] = xx * c23; p[r][2] = xx * s01; p[r][3] = xx * s23;
-                        p[r][4] = yy * s01; p[r][5] = yy * s23; p[r][6] = yy * c01; p[r][7] = yy * c23;
-                    }
+                        for (int r = 0; r < 3; ++r)
+                            p[r] = ToneAcc<kFma>::products((v2f){d[r].x, d[r].x}, (v2f){d[r].y, d[r].y}, c01, c23, s01, s23);
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) {           // ai = (ai + x*c) + y*s ; aq = (aq - x*s) + y*c (wsprd.c:200-207)
-                        acc[r].i01 = acc[r].i01 + p[r][0]; acc[r].i23 = acc[r].i23 + p[r][1];
-                        acc[r].q01 = acc[r].q01 - p[r][2]; acc[r].q23 = acc[r].q23 - p[r][3];
-                    }
+                        for (int r = 0; r < 3; ++r) acc[r].add_x(p[r]);
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) {
-                        acc[r].i01 = acc[r].i01 + p[r][4]; acc[r].i23 = acc[r].i23 + p[r][5];
-                        acc[r].q01 = acc[r].q01 + p[r][6]; acc[r].q23 = acc[r].q23 + p[r][7];
-                    }
+                        for (int r = 0; r < 3; ++r) acc[r].add_y(p[r]);
                     }
                     c4 = cn; s4 = sn;
 #pragma unroll
@@ -675,19 +646,17 @@ __device__ __forceinline__ void lagsys_wave(const float* __restrict__ xi, const 
                     const float4 c4 = cur.c[u], s4 = cur.s[u];
                     const v2f c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w}, s01 = {s4.x, s4.y}, s23 = {s4.z, s4.w};
 #pragma unroll
-                    for (int r = 0; r < R; ++r) {           // ai = (ai + x*c) + y*s ; aq = (aq - x*s) + y*c (wsprd.c:200-207)
+                    for (int r = 0; r < R; ++r) {
                         const v2f iv = S[(bb + r) % NS][q], qv = S[(bb + r) % NS][4 + q];
                         const float x = u ? iv.y : iv.x, y = u ? qv.y : qv.x;
                         const v2f xx = {x, x}, yy = {y, y};
                         if constexpr (kFma) {
-                            acc[r].step_fma(xx, yy, c01, c23, s01, s23);
+                            acc[r].step(xx, yy, c01, c23, s01, s23);
                         } else {
-                        const v2f p0 = xx * c01, p1 = xx * c23, p2 = xx * s01, p3 = xx * s23;
-                        const v2f p4 = yy * s01, p5 = yy * s23, p6 = yy * c01, p7 = yy * c23;
-                        acc[r].i01 = acc[r].i01 + p0; acc[r].i23 = acc[r].i23 + p1;
-                        acc[r].q01 = acc[r].q01 - p2; acc[r].q23 = acc[r].q23 - p3;
-                        acc[r].i01 = acc[r].i01 + p4; acc[r].i23 = acc[r].i23 + p5;
-                        acc[r].q01 = acc[r].q01 + p6; acc[r].q23 = acc[r].q23 + p7;
+                            // hand-scheduled (ToneAcc::products): a row's eight products, then its eight updates
+                            const auto p = ToneAcc<kFma>::products(xx, yy, c01, c23, s01, s23);
+                            acc[r].add_x(p);
+                            acc[r].add_y(p);
                         }
                     }
                 }
@@ -810,44 +779,18 @@ void demod_metric_kernel(const float4* __restrict__ pw, const FineState* __restr
     const int item = idx / nlag;
     if (mode == 2 && !(items[item].sync > minsync1)) return;
     const float4* __restrict__ P = pw + (size_t)idx * kNSymD;
-    float ss = 0.0f, totp = 0.0f;
-    for (int k = 0; k < kNSymD; ++k) {
-        const float4 p = P[k];
-        totp = totp + p.x + p.y + p.z + p.w;
-        const float cmet = (p.y + p.w) - (p.x + p.z);
-        ss = pr3[k] ? ss + cmet : ss - cmet;
-    }
-    ss = ss / totp;
+    const float ss = sync_metric([&](int k) { return P[k]; }, pr3);
     if (mode != 2) { sync_out[idx] = ss; return; }
     sync_out[idx] = (ss > -1e30f) ? ss : -1e30f;
-    float fsum = 0.0f, f2sum = 0.0f;
-    for (int k = 0; k < kNSymD; ++k) {
-        const float4 p = P[k];
-        const float f = pr3[k] ? p.w - p.y : p.z - p.x;
-        fsum += f / 162.0f;
-        const float ff = f * f;
-        f2sum += ff / 162.0f;
-    }
-    float fac;
-    if constexpr (kFma) {
-        fac = sqrtf(fmaf1(-fsum, fsum, f2sum));
-    } else {
-    const float m2 = fsum * fsum;
-    fac = sqrtf(f2sum - m2);
-    }
+    SoftNorm norm;
+    for (int k = 0; k < kNSymD; ++k) norm.add(soft_f(P[k], pr3[k]));
+    const float fac = norm.fac<kFma>();
     float sq = 0.0f;
     unsigned char* __restrict__ so = sym_out + (size_t)idx * kNSymD;
     for (int k = 0; k < kNSymD; ++k) {
-        const float4 p = P[k];
-        const float f = pr3[k] ? p.w - p.y : p.z - p.x;
-        float v = 50.0f * f / fac;
-        if (v > 127.0f) v = 127.0f;
-        if (v < -128.0f) v = -128.0f;
-        const float w = v + 128.0f;
-        const unsigned char b = (w == w) ? (unsigned char)(int)w : (unsigned char)0;
+        const unsigned char b = soft_quantise(soft_f(P[k], pr3[k]), fac, kSymFac);
         so[k] = b;
-        const float y = (float)b - 128.0f;
-        sq += y * y;
+        sq += soft_square(b);
     }
     rms_out[idx] = sqrtf(sq / 162.0f);
 }
@@ -881,18 +824,8 @@ void phasor_freq_kernel(const FineState* __restrict__ items, const int* __restri
     if (lane >= 4 * kNFreq) return;
     const FineState st = items[item_list[slot]];
     const int f = lane >> 2, tone = lane & 3;
-    const float f0 = kFma ? fmaf1((float)(ifmin + f), fstep, st.freq) : st.freq + (float)(ifmin + f) * fstep;
-    const float fp = (float)((double)f0 + ((double)st.drift / 2.0) * (double)(0.0f - 81.0f) / (double)81.0f);
-    const double off = (tone == 0) ? -kDf15 : (tone == 1) ? -kDf05 : (tone == 2) ? kDf05 : kDf15;
-    const float dphi = (float)(kTwoPiDt * ((double)fp + off));
-    const float cd = glibc_cosf(dphi), sd = glibc_sinf(dphi);
-    float* __restrict__ t = tabs + ((size_t)slot * kNFreq + f) * 2048;
-    float c = 1.0f, s = 0.0f;
-    for (int j = 0; j < kSps; ++j) {
-        if (j > 0) phasor_step<kFma>(c, s, cd, sd);
-        t[8 * j + tone] = c;
-        t[8 * j + 4 + tone] = s;
-    }
+    const float f0 = hyp_freq<kFma>(st.freq, ifmin + f, fstep);
+    build_phasor_table<kFma>(tone_dphi(f0, st.drift, 0, tone), tone, tabs + ((size_t)slot * kNFreq + f) * 2048);
 }
 
 constexpr int kFsThreads = 832;                                   // 13 waves: 5 x 162 = 810 working threads (freq_drift_kernel)
@@ -1044,15 +977,12 @@ void freq_drift_kernel(const float* __restrict__ dI, const float* __restrict__ d
     fetch(0);
     v2f cd01 = {1.0f, 1.0f}, cd23 = cd01, sd01 = {0.0f, 0.0f}, sd23 = sd01;
     if (working) {
-        const float f0 = kFma ? fmaf1((float)(ifmin + f), fstep, st.freq)
-                              : st.freq + (float)(ifmin + f) * fstep;          // *freq + ifreq * fstep, wsprd.c:151
-        const float fp = (float)((double)f0 + ((double)st.drift / 2.0) * (double)((float)sym - 81.0f) / (double)81.0f);
-        const double fpd = (double)fp;
+        const float f0 = hyp_freq<kFma>(st.freq, ifmin + f, fstep);
         float sn, cs;
-        glibc_sincosf_pair((float)(kTwoPiDt * (fpd - kDf15)), &sn, &cs); cd01.x = cs; sd01.x = sn;
-        glibc_sincosf_pair((float)(kTwoPiDt * (fpd - kDf05)), &sn, &cs); cd01.y = cs; sd01.y = sn;
-        glibc_sincosf_pair((float)(kTwoPiDt * (fpd + kDf05)), &sn, &cs); cd23.x = cs; sd23.x = sn;
-        glibc_sincosf_pair((float)(kTwoPiDt * (fpd + kDf15)), &sn, &cs); cd23.y = cs; sd23.y = sn;
+        glibc_sincosf_pair(tone_dphi(f0, st.drift, sym, 0), &sn, &cs); cd01.x = cs; sd01.x = sn;
+        glibc_sincosf_pair(tone_dphi(f0, st.drift, sym, 1), &sn, &cs); cd01.y = cs; sd01.y = sn;
+        glibc_sincosf_pair(tone_dphi(f0, st.drift, sym, 2), &sn, &cs); cd23.x = cs; sd23.x = sn;
+        glibc_sincosf_pair(tone_dphi(f0, st.drift, sym, 3), &sn, &cs); cd23.y = cs; sd23.y = sn;
     }
     v2f c01 = {1.0f, 1.0f}, c23 = c01, s01 = {0.0f, 0.0f}, s23 = s01;
     ToneAcc<kFma> acc;
@@ -1071,14 +1001,15 @@ void freq_drift_kernel(const float* __restrict__ dI, const float* __restrict__ d
             for (int jj = 0; jj < kFsChunk; ++jj) {
                 if (c + jj > 0) {
                     if constexpr (kFma) {
-                        const v2f n01 = fma2(c01, cd01, -(s01 * sd01)), n23 = fma2(c23, cd23, -(s23 * sd23));
-                        s01 = fma2(c01, sd01, s01 * cd01); s23 = fma2(c23, sd23, s23 * cd23);
-                        c01 = n01; c23 = n23;
+                        phasor_step<kFma>(c01, s01, cd01, sd01);
+                        phasor_step<kFma>(c23, s23, cd23, sd23);
                     } else {
-                    const v2f a01 = c01 * cd01, b01 = s01 * sd01, e01 = c01 * sd01, d01 = s01 * cd01;
-                    const v2f a23 = c23 * cd23, b23 = s23 * sd23, e23 = c23 * sd23, d23 = s23 * cd23;
-                    c01 = a01 - b01; s01 = e01 + d01;
-                    c23 = a23 - b23; s23 = e23 + d23;
+                        // hand-scheduled: the exact phasor_step() of both pairs with the eight products formed first
+                        // (as the two calls above the loop stalls, 277 -> 480 s_nop, and spills six registers)
+                        const v2f a01 = c01 * cd01, b01 = s01 * sd01, e01 = c01 * sd01, d01 = s01 * cd01;
+                        const v2f a23 = c23 * cd23, b23 = s23 * sd23, e23 = c23 * sd23, d23 = s23 * cd23;
+                        c01 = a01 - b01; s01 = e01 + d01;
+                        c23 = a23 - b23; s23 = e23 + d23;
                     }
                 }
                 acc.step(tile[sym][jj], make_float4(c01.x, c01.y, c23.x, c23.y), make_float4(s01.x, s01.y, s23.x, s23.y));
@@ -1108,14 +1039,7 @@ void freq_metric_kernel(const float4* __restrict__ pw, FineState* __restrict__ i
     for (int e = lane; e < kNFreq * kNSymD; e += 64) P[e] = pw[(size_t)slot * kNFreq * kNSymD + e];
     __syncthreads();
     if (lane < kNFreq) {
-        float ss = 0.0f, totp = 0.0f;
-        for (int k = 0; k < kNSymD; ++k) {
-            const float4 p = P[lane * kNSymD + k];
-            totp = totp + p.x + p.y + p.z + p.w;
-            const float cmet = (p.y + p.w) - (p.x + p.z);
-            ss = pr3[k] ? ss + cmet : ss - cmet;
-        }
-        met[lane] = ss / totp;
+        met[lane] = sync_metric([&](int k) { return P[lane * kNSymD + k]; }, pr3);
     }
     __syncthreads();
     if (lane == 0) {
@@ -1124,7 +1048,7 @@ void freq_metric_kernel(const float4* __restrict__ pw, FineState* __restrict__ i
         float best = -1e30f, fbest = 0.0f;
         int bshift = 0, bf = -1;
         for (int f = 0; f < kNFreq; ++f)
-            if (met[f] > best) { best = met[f]; fbest = kFma ? fmaf1((float)(ifmin + f), fstep, fin) : fin + (float)(ifmin + f) * fstep; bshift = st.shift; bf = f; }
+            if (met[f] > best) { best = met[f]; fbest = hyp_freq<kFma>(fin, ifmin + f, fstep); bshift = st.shift; bf = f; }
         st.freq = fbest;
         st.shift = bshift;
         st.sync = best;
@@ -1137,37 +1061,21 @@ void freq_metric_kernel(const float4* __restrict__ pw, FineState* __restrict__ i
     if (bf < 0) return;
     // mode 2 at (fbest, shift): same accumulators as hypothesis bf (wsprd.c:219-225, 243-256)
     for (int k = lane; k < kNSymD; k += 64) {
-        const float4 p = P[bf * kNSymD + k];
-        fsym[k] = pr3[k] ? p.w - p.y : p.z - p.x;
+        fsym[k] = soft_f(P[bf * kNSymD + k], pr3[k]);
     }
     __syncthreads();
     if (lane == 0) {
-        float fsum = 0.0f, f2sum = 0.0f;
-        for (int k = 0; k < kNSymD; ++k) {
-            const float f = fsym[k];
-            fsum += f / 162.0f;
-            const float ff = f * f;
-            f2sum += ff / 162.0f;
-        }
-        if constexpr (kFma) {
-            fac_s = sqrtf(fmaf1(-fsum, fsum, f2sum));
-        } else {
-        const float m2 = fsum * fsum;
-        fac_s = sqrtf(f2sum - m2);
-        }
+        SoftNorm norm;
+        for (int k = 0; k < kNSymD; ++k) norm.add(fsym[k]);
+        fac_s = norm.fac<kFma>();
     }
     __syncthreads();
     const float fac = fac_s;
     float sq = 0.0f;                 // sum of squares of small integers: exact in any order
     for (int k = lane; k < kNSymD; k += 64) {
-        float v = 50.0f * fsym[k] / fac;
-        if (v > 127.0f) v = 127.0f;
-        if (v < -128.0f) v = -128.0f;
-        const float w = v + 128.0f;
-        const unsigned char b = (w == w) ? (unsigned char)(int)w : (unsigned char)0;
+        const unsigned char b = soft_quantise(fsym[k], fac, kSymFac);
         sym_out[(size_t)item * kNSymD + k] = b;
-        const float y = (float)b - 128.0f;
-        sq += y * y;
+        sq += soft_square(b);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
@@ -1205,12 +1113,19 @@ __global__ void pick_freq_kernel(FineState* __restrict__ items, const int* __res
     int bshift = 0;
     for (int q = 0; q < nfreq; ++q) {
         const float v = sync_in[(size_t)it * nfreq + q];
-        if (v > best) { best = v; fbest = kFma ? fmaf1((float)(ifmin + q), fstep, fin) : fin + (float)(ifmin + q) * fstep; bshift = st.shift; }
+        if (v > best) { best = v; fbest = hyp_freq<kFma>(fin, ifmin + q, fstep); bshift = st.shift; }
     }
     st.freq = fbest;
     st.shift = bshift;
     st.sync = best;
     items[it] = st;
+}
+
+// Host side: `arith` (wspr_set_arithmetic) picks the instantiation; f receives std::true_type or std::false_type
+template <class F>
+void with_arith(int arith, F&& f) {
+    if (arith) f(std::true_type{});
+    else f(std::false_type{});
 }
 }  // namespace
 
@@ -1219,61 +1134,12 @@ void launch_demod(const float* dI, const float* dQ, int samples, const FineState
                   float minsync1, float* sync_out, unsigned char* sym_out, float* rms_out,
                   const DeviceTables& t, hipStream_t st, int symfac, int arith) {
     if (nitems <= 0 || nlag <= 0) return;
-    hipLaunchKernelGGL(arith ? demod_kernel<true> : demod_kernel<false>, dim3(nlag, nitems), dim3(192), 0, st, dI, dQ,
-                       samples, items, (const int*)nullptr, mode, nlag, lagstep, ifmin, fstep, jitter, minsync1, sync_out,
-                       sym_out, rms_out, t.sync, (float)symfac);
+    with_arith(arith, [&](auto fma) {
+        hipLaunchKernelGGL(demod_kernel<decltype(fma)::value>, dim3(nlag, nitems), dim3(192), 0, st, dI, dQ, samples, items,
+                           (const int*)nullptr, mode, nlag, lagstep, ifmin, fstep, jitter, minsync1, sync_out, sym_out,
+                           rms_out, t.sync, (float)symfac);
+    });
 }
-namespace {
-template <bool kFma>
-void launch_freq_scan_t(const float* dI, const float* dQ, int samples, FineState* items,
-                        const int* list_shared, int n_shared, const int* list_own, int n_own,
-                        int lagstep, float minsync1, const int* jitter0, float* tabs, float* pw,
-                        float* scratch_sync, float* sync_out, unsigned char* sym_out,
-                        float* rms_out, const DeviceTables& t, hipStream_t st,
-                        const float* pw_lag, int nlag_lag) {
-    // pw_lag (optional): the lag scan's amplitude block [item][nlag_lag][162] of the SAME items, still intact --
-    // the centre hypothesis is read from it instead of being summed again; pw must then be a different buffer
-    const float4* pl = reinterpret_cast<const float4*>(pw_lag);
-    // WSPR_REPEAT_FREQ / _LAG / _FANO = 2: the stage's kernels are launched twice (same outputs) -- what a stage costs
-    // INSIDE the pipelined step is the difference of two bench lines (docs/HISTORY.md section 4)
-    static const int rep_freq = [] { const char* e = lab_env("WSPR_REPEAT_FREQ"); return e ? std::max(1, atoi(e)) : 1; }();
-    // WSPR_K4_FREQ=nocentre: no centre hypothesis is taken from the lag scan (every candidate through the rare path)
-    static const bool nocentre = [] { const char* e = lab_env("WSPR_K4_FREQ"); return e && e[0] == 'n'; }();
-    const int nlag_c = (pl && !nocentre) ? nlag_lag : 0;
-    if (n_shared > 0) {
-        hipLaunchKernelGGL(phasor_freq_kernel<kFma>, dim3(n_shared), dim3(64), 0, st, items, list_shared, -2, 0.1f, tabs);
-        for (int r = 0; r < rep_freq; ++r)
-            hipLaunchKernelGGL(freq_scalar_kernel<kFma>, dim3(n_shared), dim3(kFqThreads), 0, st, dI, dQ, samples, items,
-                               list_shared, tabs, reinterpret_cast<float4*>(pw), pl, nlag_c, lagstep);
-        hipLaunchKernelGGL(freq_centre_rare_kernel<kFma>, dim3(n_shared), dim3(64), 0, st, dI, dQ, samples, items, list_shared,
-                           tabs, reinterpret_cast<float4*>(pw), nlag_c, lagstep);
-        hipLaunchKernelGGL(freq_metric_kernel<kFma>, dim3(n_shared), dim3(64), 0, st,
-                           reinterpret_cast<const float4*>(pw), items, list_shared, n_shared, -2, 0.1f, minsync1,
-                           sync_out, sym_out, rms_out, t.sync);
-    }
-    if (n_own > 0) {
-        static const bool general = [] { const char* e = lab_env("WSPR_K4_DRIFT"); return e && e[0] == 't'; }();
-        if (!general) {
-            // pw rows of the drifting candidates follow those of the drift-free ones
-            float4* pw_own = reinterpret_cast<float4*>(pw) + (size_t)n_shared * kNFreq * kNSymD;
-            for (int r = 0; r < rep_freq; ++r)
-            hipLaunchKernelGGL(freq_drift_kernel<kFma>, dim3(n_own), dim3(kFsThreads), 0, st, dI, dQ, samples, items, list_own,
-                               -2, 0.1f, pw_own, nocentre ? nullptr : pl, nlag_lag, lagstep);
-            hipLaunchKernelGGL(freq_metric_kernel<kFma>, dim3(n_own), dim3(64), 0, st, pw_own, items, list_own, n_own, -2, 0.1f,
-                               minsync1, sync_out, sym_out, rms_out, t.sync);
-            return;
-        }
-        // scratch_sync is indexed [item][5] by the general kernel
-        hipLaunchKernelGGL(demod_kernel<kFma>, dim3(kNFreq, n_own), dim3(192), 0, st, dI, dQ, samples, items, list_own, 1,
-                           kNFreq, lagstep, -2, 0.1f, (const int*)nullptr, 0.0f, scratch_sync, (unsigned char*)nullptr,
-                           (float*)nullptr, t.sync, 50.0f);
-        hipLaunchKernelGGL(pick_freq_kernel<kFma>, dim3((n_own + 63) / 64), dim3(64), 0, st, items, list_own, n_own,
-                           scratch_sync, kNFreq, -2, 0.1f);
-        hipLaunchKernelGGL(demod_kernel<kFma>, dim3(1, n_own), dim3(192), 0, st, dI, dQ, samples, items, list_own, 2, 1,
-                           lagstep, 0, 0.0f, jitter0, minsync1, sync_out, sym_out, rms_out, t.sync, 50.0f);
-    }
-}
-}  // namespace
 
 // Frequency scan (5 hypotheses at +-0.2 Hz, step 0.1) followed by the first ladder rung.
 // Drift-free candidates (list_shared) take the fused tiled path; drifting ones (list_own) the
@@ -1284,63 +1150,103 @@ void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int sampl
                                      float* scratch_sync, float* sync_out, unsigned char* sym_out,
                                      float* rms_out, const DeviceTables& t, hipStream_t st,
                                      const float* pw_lag, int nlag_lag, int arith) {
-    if (arith) launch_freq_scan_t<true>(dI, dQ, samples, items, list_shared, n_shared, list_own, n_own, lagstep, minsync1,
-                                        jitter0, tabs, pw, scratch_sync, sync_out, sym_out, rms_out, t, st, pw_lag, nlag_lag);
-    else launch_freq_scan_t<false>(dI, dQ, samples, items, list_shared, n_shared, list_own, n_own, lagstep, minsync1,
-                                   jitter0, tabs, pw, scratch_sync, sync_out, sym_out, rms_out, t, st, pw_lag, nlag_lag);
+    // pw_lag (optional): the lag scan's amplitude block [item][nlag_lag][162] of the SAME items, still intact --
+    // the centre hypothesis is read from it instead of being summed again; pw must then be a different buffer
+    const float4* pl = reinterpret_cast<const float4*>(pw_lag);
+    // WSPR_REPEAT_FREQ / _LAG / _FANO = 2: the stage's kernels are launched twice (same outputs) -- what a stage costs
+    // INSIDE the pipelined step is the difference of two bench lines (docs/HISTORY.md section 4)
+    static const int rep_freq = [] { const char* e = lab_env("WSPR_REPEAT_FREQ"); return e ? std::max(1, atoi(e)) : 1; }();
+    // WSPR_K4_FREQ=nocentre: no centre hypothesis is taken from the lag scan (every candidate through the rare path)
+    static const bool nocentre = [] { const char* e = lab_env("WSPR_K4_FREQ"); return e && e[0] == 'n'; }();
+    static const bool general = [] { const char* e = lab_env("WSPR_K4_DRIFT"); return e && e[0] == 't'; }();
+    const int nlag_c = (pl && !nocentre) ? nlag_lag : 0;
+    with_arith(arith, [&](auto fma) {
+        constexpr bool kFma = decltype(fma)::value;
+        if (n_shared > 0) {
+            hipLaunchKernelGGL(phasor_freq_kernel<kFma>, dim3(n_shared), dim3(64), 0, st, items, list_shared, -2, 0.1f, tabs);
+            for (int r = 0; r < rep_freq; ++r)
+                hipLaunchKernelGGL(freq_scalar_kernel<kFma>, dim3(n_shared), dim3(kFqThreads), 0, st, dI, dQ, samples, items,
+                                   list_shared, tabs, reinterpret_cast<float4*>(pw), pl, nlag_c, lagstep);
+            hipLaunchKernelGGL(freq_centre_rare_kernel<kFma>, dim3(n_shared), dim3(64), 0, st, dI, dQ, samples, items,
+                               list_shared, tabs, reinterpret_cast<float4*>(pw), nlag_c, lagstep);
+            hipLaunchKernelGGL(freq_metric_kernel<kFma>, dim3(n_shared), dim3(64), 0, st,
+                               reinterpret_cast<const float4*>(pw), items, list_shared, n_shared, -2, 0.1f, minsync1,
+                               sync_out, sym_out, rms_out, t.sync);
+        }
+        if (n_own > 0 && !general) {
+            // pw rows of the drifting candidates follow those of the drift-free ones
+            float4* pw_own = reinterpret_cast<float4*>(pw) + (size_t)n_shared * kNFreq * kNSymD;
+            for (int r = 0; r < rep_freq; ++r)
+                hipLaunchKernelGGL(freq_drift_kernel<kFma>, dim3(n_own), dim3(kFsThreads), 0, st, dI, dQ, samples, items,
+                                   list_own, -2, 0.1f, pw_own, nocentre ? nullptr : pl, nlag_lag, lagstep);
+            hipLaunchKernelGGL(freq_metric_kernel<kFma>, dim3(n_own), dim3(64), 0, st, pw_own, items, list_own, n_own, -2,
+                               0.1f, minsync1, sync_out, sym_out, rms_out, t.sync);
+        } else if (n_own > 0) {
+            // scratch_sync is indexed [item][5] by the general kernel
+            hipLaunchKernelGGL(demod_kernel<kFma>, dim3(kNFreq, n_own), dim3(192), 0, st, dI, dQ, samples, items, list_own,
+                               1, kNFreq, lagstep, -2, 0.1f, (const int*)nullptr, 0.0f, scratch_sync,
+                               (unsigned char*)nullptr, (float*)nullptr, t.sync, kSymFac);
+            hipLaunchKernelGGL(pick_freq_kernel<kFma>, dim3((n_own + 63) / 64), dim3(64), 0, st, items, list_own, n_own,
+                               scratch_sync, kNFreq, -2, 0.1f);
+            hipLaunchKernelGGL(demod_kernel<kFma>, dim3(1, n_own), dim3(192), 0, st, dI, dQ, samples, items, list_own, 2, 1,
+                               lagstep, 0, 0.0f, jitter0, minsync1, sync_out, sym_out, rms_out, t.sync, kSymFac);
+        }
+    });
 }
 
 void launch_phasor_tables(const FineState* items, int nitems, int mode, float* tabs, hipStream_t st, int arith) {
     if (nitems <= 0) return;
-    hipLaunchKernelGGL(arith ? phasor_table_kernel<true> : phasor_table_kernel<false>, dim3(1, nitems), dim3(64), 0, st,
-                       items, mode, tabs);
+    with_arith(arith, [&](auto fma) {
+        hipLaunchKernelGGL(phasor_table_kernel<decltype(fma)::value>, dim3(1, nitems), dim3(64), 0, st, items, mode, tabs);
+    });
 }
 
 namespace {
-template <bool kFma>
-void launch_demod_tiled_t(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
-                          const int* list_shared, int n_shared, const int* list_own, int n_own, int mode,
-                          int nlag, int lagstep, float minsync1, const float* tabs, float* pw,
-                          float* sync_out, unsigned char* sym_out, float* rms_out,
-                          const DeviceTables& t, hipStream_t st) {
-    auto tile_bytes = [&](int syms) {
-        const int span = kSps * syms + lagstep * (nlag - 1);
-        const int pitch = (span + lagstep - 1) / lagstep + 1;
-        return (size_t)pitch * lagstep * sizeof(float2);
-    };
-    auto threads = [&](int syms) { return dim3(((syms * nlag + 63) / 64) * 64); };
-    float4* pw4 = reinterpret_cast<float4*>(pw);
+// What one tiled lag scan works on (launch_demod_tiled's arguments)
+struct TiledScan {
+    const float *dI, *dQ;
+    int samples;
+    const FineState* items;
+    const int *list_shared, *list_own;
+    int n_shared, n_own, mode, nlag;
+    float minsync1;
+    const float* tabs;
+    float4* pw4;
+    hipStream_t st;
+};
+
+// The amplitude kernels of a tiled scan at lag step STEP: drift-free candidates, then drifting ones
+template <int STEP, bool kFma>
+void launch_tile(const TiledScan& a) {
     // WSPR_K4_LAG=tile: drift-free candidates' full lag scan on demod_tile_kernel<8, true> (one (symbol, lag) per lane,
     // samples in LDS) instead of the register-resident correlation
     static const bool lagsys_kernel = [] { const char* e = lab_env("WSPR_K4_LAG"); return !(e && e[0] == 't'); }();
     // WSPR_K4_DRIFT=tile: drifting candidates' full lag scan on demod_tile_kernel<8, false> (one lag per lane)
     static const bool drift_kernel = [] { const char* e = lab_env("WSPR_K4_DRIFT"); return !(e && e[0] == 't'); }();
     static const int rep_lag = [] { const char* e = lab_env("WSPR_REPEAT_LAG"); return e ? std::max(1, atoi(e)) : 1; }();
-#define WSPR_LAUNCH_TILE(STEP)                                                                                   \
-    do {                                                                                                         \
-        if (n_shared > 0 && STEP == 8 && nlag == 33 && mode == 0 && lagsys_kernel)                               \
-            for (int r_ = 0; r_ < rep_lag; ++r_)                                                                 \
-            hipLaunchKernelGGL(demod_lagsys_kernel<kFma>, dim3(kSysWaves * ((n_shared + 7) & ~7) + (n_shared + 63) / 64), dim3(64), 0, st, \
-                               dI, dQ, samples, items, list_shared, n_shared, tabs, pw4);                        \
-        else if (n_shared > 0)                                                                                   \
-            hipLaunchKernelGGL((demod_tile_kernel<STEP, true, kFma>), dim3(kNSymD / kTileSymsShared, n_shared),        \
-                               threads(kTileSymsShared), tile_bytes(kTileSymsShared), st, dI, dQ, samples,        \
-                               items, list_shared, mode, nlag, minsync1, tabs, pw4);                             \
-        if (n_own > 0 && STEP == 8 && nlag == 33 && mode == 0 && drift_kernel)                                   \
-            for (int r_ = 0; r_ < rep_lag; ++r_)                                                                 \
-            hipLaunchKernelGGL(demod_drift_kernel<kFma>, dim3((kNSymD + kDrSyms - 1) / kDrSyms, n_own), dim3(64), 0, st, \
-                               dI, dQ, samples, items, list_own, pw4);                                           \
-        else if (n_own > 0)                                                                                      \
-            hipLaunchKernelGGL((demod_tile_kernel<STEP, false, kFma>), dim3(kNSymD / kTileSymsOwn, n_own),             \
-                               threads(kTileSymsOwn), kTileSymsOwn * kOwnTabPitch * 16 + tile_bytes(kTileSymsOwn), st, dI, dQ, \
-                               samples, items, list_own, mode, nlag, minsync1, tabs, pw4);                       \
-    } while (0)
-    if (lagstep == 8) WSPR_LAUNCH_TILE(8);
-    else if (lagstep == 16) WSPR_LAUNCH_TILE(16);
-    else WSPR_LAUNCH_TILE(3);
-#undef WSPR_LAUNCH_TILE
-    hipLaunchKernelGGL(demod_metric_kernel<kFma>, dim3((nitems * nlag + 63) / 64), dim3(64), 0, st, pw4, items, nitems,
-                       mode, nlag, minsync1, sync_out, sym_out, rms_out, t.sync);
+    auto tile_bytes = [&](int syms) {
+        const int span = kSps * syms + STEP * (a.nlag - 1);
+        const int pitch = (span + STEP - 1) / STEP + 1;
+        return (size_t)pitch * STEP * sizeof(float2);
+    };
+    auto threads = [&](int syms) { return dim3(((syms * a.nlag + 63) / 64) * 64); };
+    const bool full_scan = STEP == 8 && a.nlag == 33 && a.mode == 0;
+    if (a.n_shared > 0 && full_scan && lagsys_kernel)
+        for (int r = 0; r < rep_lag; ++r)
+            hipLaunchKernelGGL(demod_lagsys_kernel<kFma>, dim3(kSysWaves * ((a.n_shared + 7) & ~7) + (a.n_shared + 63) / 64),
+                               dim3(64), 0, a.st, a.dI, a.dQ, a.samples, a.items, a.list_shared, a.n_shared, a.tabs, a.pw4);
+    else if (a.n_shared > 0)
+        hipLaunchKernelGGL((demod_tile_kernel<STEP, true, kFma>), dim3(kNSymD / kTileSymsShared, a.n_shared),
+                           threads(kTileSymsShared), tile_bytes(kTileSymsShared), a.st, a.dI, a.dQ, a.samples, a.items,
+                           a.list_shared, a.mode, a.nlag, a.minsync1, a.tabs, a.pw4);
+    if (a.n_own > 0 && full_scan && drift_kernel)
+        for (int r = 0; r < rep_lag; ++r)
+            hipLaunchKernelGGL(demod_drift_kernel<kFma>, dim3((kNSymD + kDrSyms - 1) / kDrSyms, a.n_own), dim3(64), 0, a.st,
+                               a.dI, a.dQ, a.samples, a.items, a.list_own, a.pw4);
+    else if (a.n_own > 0)
+        hipLaunchKernelGGL((demod_tile_kernel<STEP, false, kFma>), dim3(kNSymD / kTileSymsOwn, a.n_own),
+                           threads(kTileSymsOwn), kTileSymsOwn * kOwnTabPitch * 16 + tile_bytes(kTileSymsOwn), a.st, a.dI,
+                           a.dQ, a.samples, a.items, a.list_own, a.mode, a.nlag, a.minsync1, a.tabs, a.pw4);
 }
 }  // namespace
 
@@ -1351,10 +1257,16 @@ void launch_demod_tiled(const float* dI, const float* dQ, int samples, const Fin
                         float* sync_out, unsigned char* sym_out, float* rms_out,
                         const DeviceTables& t, hipStream_t st, int arith) {
     if (nitems <= 0) return;
-    if (arith) launch_demod_tiled_t<true>(dI, dQ, samples, items, nitems, list_shared, n_shared, list_own, n_own, mode, nlag,
-                                          lagstep, minsync1, tabs, pw, sync_out, sym_out, rms_out, t, st);
-    else launch_demod_tiled_t<false>(dI, dQ, samples, items, nitems, list_shared, n_shared, list_own, n_own, mode, nlag,
-                                     lagstep, minsync1, tabs, pw, sync_out, sym_out, rms_out, t, st);
+    const TiledScan a{dI, dQ, samples, items, list_shared, list_own, n_shared, n_own, mode, nlag, minsync1, tabs,
+                      reinterpret_cast<float4*>(pw), st};
+    with_arith(arith, [&](auto fma) {
+        constexpr bool kFma = decltype(fma)::value;
+        if (lagstep == 8) launch_tile<8, kFma>(a);
+        else if (lagstep == 16) launch_tile<16, kFma>(a);
+        else launch_tile<3, kFma>(a);
+        hipLaunchKernelGGL(demod_metric_kernel<kFma>, dim3((nitems * nlag + 63) / 64), dim3(64), 0, st, a.pw4, items, nitems,
+                           mode, nlag, minsync1, sync_out, sym_out, rms_out, t.sync);
+    });
 }
 
 #ifdef WSPR_LAB   // calibration kernel: lab build only

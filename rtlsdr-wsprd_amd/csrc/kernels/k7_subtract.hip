@@ -17,6 +17,7 @@
 //                          c*r/norm in place with r from LDS.
 // Bound: fp32 VALU (64 MFLOP of separately rounded mul/add per job), not HBM.
 #include "wspr_device.h"
+#include "arith.h"
 #include <cstdlib>
 #include "glibc_sincosf.h"
 #include "phase_runs.h"
@@ -155,9 +156,9 @@ constexpr int kHalo = kLpfTaps / 2;                               // 180 samples
 // for the epilogue.  Set 3.13 -> 2.89 ms per 2 048 jobs, 664 KB of scratch per job gone.
 // Staging goes symbol by symbol (thread j = sample j of the symbol), so that a wave sits in ONE symbol and fetches
 // its few runs with wave-uniform (scalar) loads.
-// kFma (wspr_set_arithmetic): the contracted mode fuses the three sites of wsprd.c:378-409 as clang's -ffp-contract=on
-// does, left product first: ci = fma(x, cr, y*sr), cq = fma(y, cr, -(x*sr)); cfi = fma(w, ci, cfi) (one v_pk_fma_f32 per
-// tap and output pair); ri = fma(cfi, refi, -(cfq*refq)), rq = fma(cfi, refq, cfq*refi).
+// kFma (wspr_set_arithmetic): the three sites of wsprd.c:378-409 go through Arith<kFma> (arith.h): ci = x*cr + y*sr,
+// cq = y*cr - x*sr; cfi = cfi + w*ci (packed: one instruction per tap and output pair); ri = cfi*refi - cfq*refq,
+// rq = cfi*refq + cfq*refi.
 template <bool kFma>
 __global__ __launch_bounds__(kFirThreads)
 void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np,
@@ -166,7 +167,7 @@ void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np
                           int parity) {
     __shared__ float2 tile[8 * kFir8Pitch];
     __shared__ float2 rref[kFir8Out];
-    typedef float v2f __attribute__((ext_vector_type(2)));
+    using A = Arith<kFma>;
     const int tid = threadIdx.x;
     // staging (loads, sincos: short dependent chains that want to issue at once) runs at a higher wave priority than the
     // FIR loop, which fills whatever issue slots are left: 2.58 -> 2.50 ms per 2 048 jobs
@@ -229,14 +230,8 @@ void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np
         float a = 0.0f, b = 0.0f;
         if (k > 0 && k < np) {
             const float x = xi[k], y = xq[k];
-            if constexpr (kFma) {
-                a = __builtin_fmaf(x, cr, y * sr);
-                b = __builtin_fmaf(y, cr, -(x * sr));
-            } else {
-            const float p1 = x * cr, p2 = y * sr, p3 = y * cr, p4 = x * sr;
-            a = p1 + p2;                  // Re{s conj(r)}
-            b = p3 - p4;                  // Im{s conj(r)}
-            }
+            a = A::mma(x, cr, y, sr);     // Re{s conj(r)}
+            b = A::mms(y, cr, x, sr);     // Im{s conj(r)}
         }
         const int e = n - n_lo;
         tile[(e & 7) * kFir8Pitch + (e >> 3)] = make_float2(a, b);
@@ -280,22 +275,13 @@ void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const v2f wu = {w[u], w[u]};
-            if constexpr (kFma) {
-#pragma unroll
-                for (int r = 0; r < 8; ++r) {
-                    const int i = (u + r) & 7;
-                    acc[r] = __builtin_elementwise_fma(wu, i < u ? in[i] : old[i], acc[r]);
-                }
-                continue;
-            }
-            v2f p[8];
+            v2f x[8];                                    // the window at tap u: in[0..u-1] | old[u..7], from output r's side
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 const int i = (u + r) & 7;
-                p[r] = wu * (i < u ? in[i] : old[i]);
+                x[r] = i < u ? in[i] : old[i];
             }
-#pragma unroll
-            for (int r = 0; r < 8; ++r) acc[r] = acc[r] + p[r];
+            A::mad_each(wu, x, acc);
         }
     };
     __builtin_amdgcn_s_setprio(0);
@@ -324,14 +310,7 @@ void sub_fir_fused_kernel(float* __restrict__ dI, float* __restrict__ dQ, int np
         if (k > 0 && k < np) {
             const float2 rr = rref[8 * tid + r];
             const float si = acc[r].x, sq = acc[r].y;
-            float ri, rq;
-            if constexpr (kFma) {
-                ri = __builtin_fmaf(si, rr.x, -(sq * rr.y));
-                rq = __builtin_fmaf(si, rr.y, sq * rr.x);
-            } else {
-            const float a = si * rr.x, b = sq * rr.y, c = si * rr.y, d = sq * rr.x;
-            ri = a - b; rq = c + d;
-            }
+            float ri = A::mms(si, rr.x, sq, rr.y), rq = A::mma(si, rr.y, sq, rr.x);
             if (edge_tile) {
                 float norm = 1.0f;
                 if (n < kLpfTaps / 2)                    norm = lpf_part[kLpfTaps / 2 + n];
