@@ -10,16 +10,20 @@
  *   coherent subtraction           wsprd/wsprd.c:316-413  (subtract_signal2)
  *   decode orchestration           wsprd/wsprd.c:416-855  (wspr_decode)
  *
- * PARITY PIN.  wsprd/wsprd.c cannot be compiled in this image: it needs
- * <fftw3.h>/libfftw3f (un-vendored, unpinned system library, Makefile:3) which
- * is absent, and no stand-in is written for it.  This restatement is therefore
- * pinned by (tests/test_oracle_golden.py):
- *   - the reference's documented spot lines for signals/refSignalSnr0dB.iq and
- *     for the -t self-test (documentation/bug-fix/REPORT.md:198,202),
- *   - the self-test acceptance rule of rtlsdr_wsprd.c:782-788,
- *   - the per-stage anchor values recorded from the reference in SURVEY.md §8(c).
- * The FFT itself (FFTW codelets in the reference) is float32 radix-2 here and is
- * only tolerance-comparable (no reference test pins FFT output).
+ * PARITY PIN.  This restatement is pinned to the reference's own wsprd/wsprd.c,
+ * compiled where it lies (oracle/Makefile: _ref/libwsprd_dsp_ref.so; gcc, x86-64,
+ * no fused multiply-add): wspr_decode, sync_and_demodulate, subtract_signal and
+ * subtract_signal2 give the same spots (every field, snr included) and the same
+ * residual IQ bit for bit, over option sets, random and crowded scenes, both
+ * loop exits, equal-snr ties, short records and finite extremes
+ * (tests/test_reference_pin.py).  The FFT is the one thing substituted: the
+ * reference's FFTW (an un-vendored system library whose codelets depend on
+ * version, flags and CPU) is replaced there by orc_fft512 below, behind the
+ * <fftw3.h> stand-in of oracle/standin/.  The FFT itself is float32 radix-2 and
+ * is only tolerance-comparable with FFTW (no reference test pins FFT
+ * output).  The reference's documented spot lines (REPORT.md:198,202), the
+ * self-test rule of rtlsdr_wsprd.c:782-788 and the stage anchors of SURVEY §8(c)
+ * are pinned as before (tests/test_oracle_golden.py).
  *
  * Build with -ffp-contract=off (oracle/Makefile).
  * ==========================================================================*/

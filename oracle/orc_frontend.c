@@ -6,10 +6,13 @@
  *   tail zero-fill + max-abs normalisation to 0.5        rtlsdr_wsprd.c:284-305
  *   .iq file convention (Q negated, normalise)           rtlsdr_wsprd.c:555-592
  *
- * PARITY UNPINNED for the decimator: rtlsdr_wsprd.c needs <rtl-sdr.h>, libusb and
- * libcurl headers that are absent from this image (no stand-ins are written), the
- * callback is `static`, and no reference test or fixture holds decimator output.
- * The restatement is checked by construction properties only (tests/).
+ * PARITY PIN.  The decimator is pinned to the reference's own callback: rtlsdr_wsprd.c is
+ * compiled where it lies behind declaration-only <rtl-sdr.h> and <curl/curl.h> stand-ins
+ * (oracle/standin/, oracle/Makefile: _ref/librtlsdr_front_ref.so), a wrapper feeds its
+ * `static` callback, and every output equals orc_decim_feed()'s bit for bit, chunk for chunk,
+ * up to a full frame that saturates at 45000 outputs (tests/test_reference_pin_frontend.py).
+ * Its readRawIQfile, readC2file and writeRawIQfile pin the .iq convention
+ * (tests/test_file_formats.py).
  * ==========================================================================*/
 #include "wspr_oracle.h"
 

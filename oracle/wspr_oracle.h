@@ -9,7 +9,10 @@
  * link or call this library, and only as the checker.  The product
  * (libwspr_mi355x.so) never includes, links or calls anything in oracle/.
  *
- * Every function cites the reference file:line it restates.
+ * Every function cites the reference file:line it restates.  The DSP stages and
+ * the decimator are pinned to the reference's own compiled wsprd.c and
+ * rtlsdr_wsprd.c (oracle/Makefile, _ref/; tests/test_reference_pin*.py); the FFT
+ * is the one thing substituted there (orc_fft512 behind an <fftw3.h> stand-in).
  * ==========================================================================*/
 #pragma once
 #include <stddef.h>

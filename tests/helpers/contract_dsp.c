@@ -26,6 +26,14 @@
  * Everything without a site (the FFT butterflies, peak picking, coarse sync,
  * Fano, the message layer) is oracle/liboracle.so's, linked, not restated.
  *
+ * PIN.  The table above is pinned to the reference's own wsprd.c as clang compiles it with
+ * -ffp-contract=on -mfma (oracle/Makefile: _ref/libwsprd_dsp_ref_fma.so, the oracle's FFT behind an
+ * <fftw3.h> stand-in): the CONTRACT=1 build gives that library's spots and residual IQ bit for bit
+ * (tests/test_reference_pin.py), so the table is right and complete for wspr_decode,
+ * sync_and_demodulate and subtract_signal2.  Two limits: site 249 feeds only the truncation of the
+ * soft symbols to bytes, where one rounding is all but invisible; and subtract_signal()
+ * (wsprd.c:263-312, never called by the decoder) has no site here although clang fuses inside it.
+ *
  * Build with -ffp-contract=off so that the host compiler adds no fusion of its own.
  * ==========================================================================*/
 #include "wspr_oracle.h"

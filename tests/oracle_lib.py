@@ -1,9 +1,15 @@
-"""ctypes bindings of the CPU oracle (oracle/liboracle.so) and of the real reference
-message-layer objects (oracle/_ref/libwsprd_ref.so).  TEST INFRASTRUCTURE ONLY:
-imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg."""
+"""ctypes bindings of the CPU oracle (oracle/liboracle.so) and of the real reference, compiled by oracle/Makefile
+into oracle/_ref/: the message-layer objects (libwsprd_ref.so), the decoder wsprd.c in an exact and a clang-fused
+build (libwsprd_dsp_ref.so, libwsprd_dsp_ref_fma.so) and the receiver's decimator callback and file readers
+(librtlsdr_front_ref.so).  TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's
+cpu_baseline leg (those two use the oracle alone)."""
+import contextlib
 import ctypes as C
 import os
+import shutil
 import subprocess
+import tempfile
+import threading
 
 import numpy as np
 
@@ -147,6 +153,185 @@ def ref_lib():
 
 def ptr(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+# ---------------------------------------------------------------------------------------- the compiled reference
+# The reference is not re-entrant (wsprd.c keeps its FFT plan in a global), and wspr_decode leaves files in the working
+# directory (an empty fftw_wisdom.dat; hashtable.txt under usehashtable): one lock around every call, and every call
+# runs inside a temporary directory.
+_ref_lock = threading.RLock()
+_ref_tmp = None
+_DEMOD_ARGS = [C.c_void_p, C.c_void_p, C.c_long, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+               C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+_SUBTRACT_ARGS = [C.c_void_p, C.c_void_p, C.c_long, C.c_float, C.c_int, C.c_float, C.c_void_p]
+
+
+@contextlib.contextmanager
+def working_directory(cwd=None):
+    """Hold the reference lock and run inside cwd (default: one temporary directory kept for the process)."""
+    global _ref_tmp
+    with _ref_lock:
+        if cwd is None:
+            if _ref_tmp is None:
+                _ref_tmp = tempfile.TemporaryDirectory(prefix="wspr_ref_cwd_")
+            cwd = _ref_tmp.name
+        back = os.getcwd()
+        os.chdir(cwd)
+        try:
+            yield
+        finally:
+            os.chdir(back)
+
+
+def _bind_dsp(R):
+    R.wspr_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_int, Options, C.c_void_p, C.c_void_p]
+    R.wspr_decode.restype = C.c_int
+    R.sync_and_demodulate.argtypes = _DEMOD_ARGS
+    R.sync_and_demodulate.restype = None
+    for f in (R.subtract_signal, R.subtract_signal2):
+        f.argtypes = _SUBTRACT_ARGS
+        f.restype = None
+
+
+class RefDsp:
+    """The reference's own wsprd.c, compiled; the one thing substituted is the FFT (the oracle's orc_fft512 behind an
+    <fftw3.h> stand-in).  Methods take what the C functions take."""
+
+    def __init__(self, path):
+        lib()                                                   # liboracle.so first: the library needs orc_fft512 from it
+        self.path = path
+        self._lib = C.CDLL(path, mode=C.RTLD_LOCAL)
+        _bind_dsp(self._lib)
+
+    def decode(self, I, Q, samples=None, opt=None, cwd=None):
+        """wspr_decode on copies of I/Q: (spots, residual I, Q).  cwd: where hashtable.txt lives (usehashtable)."""
+        I = np.ascontiguousarray(I, dtype=np.float32).copy()
+        Q = np.ascontiguousarray(Q, dtype=np.float32).copy()
+        n = int(samples if samples is not None else I.size)
+        spots = (Spot * 100)()
+        nres = C.c_int(0)
+        with working_directory(cwd):
+            self._lib.wspr_decode(ptr(I), ptr(Q), n, opt or default_options(), C.addressof(spots), C.addressof(nres))
+        return [spots[i] for i in range(nres.value)], I, Q
+
+    def sync_and_demodulate(self, *args):
+        with working_directory():
+            self._lib.sync_and_demodulate(*args)
+
+    def subtract_signal(self, *args):
+        with working_directory():
+            self._lib.subtract_signal(*args)
+
+    def subtract_signal2(self, *args):
+        with working_directory():
+            self._lib.subtract_signal2(*args)
+
+
+_ref_dsp = {}
+
+
+def _ref_dsp_named(name):
+    if name not in _ref_dsp:
+        path = os.path.join(ORACLE_DIR, "_ref", name)
+        if not os.path.exists(path):
+            return None
+        _ref_dsp[name] = RefDsp(path)
+    return _ref_dsp[name]
+
+
+def ref_dsp_lib():
+    """wsprd.c as gcc builds it for x86-64 (no fused multiply-add).  None when the library is not present."""
+    return _ref_dsp_named("libwsprd_dsp_ref.so")
+
+
+def cpu_has_fma():
+    try:
+        with open("/proc/cpuinfo") as f:
+            return any(line.startswith("flags") and " fma " in line + " " for line in f)
+    except OSError:
+        return False
+
+
+def ref_dsp_fma_lib():
+    """wsprd.c as clang builds it with -ffp-contract=on -mfma.  None when the library is not present or the CPU has
+    no FMA instructions to run it."""
+    return _ref_dsp_named("libwsprd_dsp_ref_fma.so") if cpu_has_fma() else None
+
+
+class RefFrontEnd:
+    """One instance of the reference's rtlsdr_wsprd.c: its decimator callback with state of its own, and its file
+    readers and writer.  The callback's state is function-static and cannot be reset, so every instance is a fresh
+    copy of the library (beside a link to liboracle.so, which its decoder half needs)."""
+
+    def __init__(self, path):
+        lib()
+        self._dir = tempfile.TemporaryDirectory(prefix="wspr_front_ref_")
+        os.mkdir(os.path.join(self._dir.name, "_ref"))
+        os.symlink(os.path.join(ORACLE_DIR, "liboracle.so"), os.path.join(self._dir.name, "liboracle.so"))
+        copy = os.path.join(self._dir.name, "_ref", os.path.basename(path))
+        shutil.copy(path, copy)
+        R = C.CDLL(copy, mode=C.RTLD_LOCAL)
+        R.front_ref_feed.argtypes = [C.c_void_p, C.c_uint32]
+        R.front_ref_feed.restype = None
+        R.front_ref_count.restype = C.c_uint32
+        R.front_ref_read.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
+        R.front_ref_read.restype = None
+        for f in (R.readRawIQfile, R.readC2file, R.writeRawIQfile):
+            f.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
+            f.restype = C.c_int32
+        R.decoderSelfTest.restype = C.c_int32
+        self._lib = R
+
+    def feed(self, chunk):
+        """One callback's worth of interleaved u8 IQ; returns the number of outputs so far.  The callback rewrites
+        its buffer in place, so it gets a copy."""
+        buf = np.array(chunk, dtype=np.uint8, copy=True)
+        with working_directory():
+            self._lib.front_ref_feed(ptr(buf), buf.size)
+            return self._lib.front_ref_count()
+
+    def outputs(self):
+        with working_directory():
+            n = self._lib.front_ref_count()
+            I = np.zeros(NSAMP, np.float32)
+            Q = np.zeros(NSAMP, np.float32)
+            self._lib.front_ref_read(ptr(I), ptr(Q), n)
+        return I, Q, n
+
+    def read_iq(self, path):
+        return self._read(self._lib.readRawIQfile, path)
+
+    def read_c2(self, path):
+        return self._read(self._lib.readC2file, path)
+
+    def _read(self, fn, path):
+        I = np.zeros(NSAMP, np.float32)
+        Q = np.zeros(NSAMP, np.float32)
+        with working_directory():
+            n = fn(ptr(I), ptr(Q), os.path.abspath(path).encode())
+        return I, Q, n
+
+    def write_iq(self, I, Q, path):
+        I = np.ascontiguousarray(I, dtype=np.float32)
+        Q = np.ascontiguousarray(Q, dtype=np.float32)
+        assert I.size == NSAMP and Q.size == NSAMP
+        with working_directory():
+            return self._lib.writeRawIQfile(ptr(I), ptr(Q), os.path.abspath(path).encode())
+
+    def self_test(self):
+        """decoderSelfTest() under the receiver's default decoder options: 1 when the reference decodes its own
+        synthesised signal (it prints the spot and leaves selftest.iq in the temporary directory)."""
+        with working_directory():
+            self._lib.initDecoder_options()
+            return self._lib.decoderSelfTest()
+
+
+def ref_front_end():
+    """A fresh instance of the compiled reference receiver.  None when the library is not present."""
+    path = os.path.join(ORACLE_DIR, "_ref", "librtlsdr_front_ref.so")
+    if not os.path.exists(path):
+        return None
+    return RefFrontEnd(path)
 
 
 def read_iq_file(path):

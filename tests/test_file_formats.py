@@ -1,10 +1,13 @@
 """recorded-file readers/writer and the playback spot line of the C ABI
-(host code, no GPU) against the oracle's reader semantics and the reference's documented output."""
+(host code, no GPU) against the oracle's reader semantics and the reference's documented output; and the oracle's
+reader, with the C ABI's readers and writer, against the reference's own compiled readRawIQfile, readC2file and
+writeRawIQfile (oracle/_ref/librtlsdr_front_ref.so)."""
 import ctypes as C
 import os
 import struct
 
 import numpy as np
+import pytest
 
 import oracle_lib as ol
 import rtlsdr_wsprd_amd as w
@@ -49,6 +52,58 @@ def test_iq_write_read_roundtrip_and_c2(tmp_path):
     assert dial.value == 14095600.0
     sc = np.float32(0.5 / float(max(np.abs(I[:40000]).max(), np.abs(Q[:40000]).max())))
     assert np.array_equal(I3[:40000], I[:40000] * sc) and not I3[40000:].any()
+
+
+def _front():
+    fe = ol.ref_front_end()
+    if fe is None:
+        pytest.skip("oracle/_ref/librtlsdr_front_ref.so is not built (the reference is not mounted)")
+    return fe
+
+
+def test_compiled_reference_reader_equals_oracle_reader_on_the_golden_file():
+    fe = _front()
+    ri, rq, rn = fe.read_iq(REF_IQ)
+    oi, oq, on = ol.read_iq_file(REF_IQ)
+    assert rn == on == 45000
+    assert ri.tobytes() == oi.tobytes() and rq.tobytes() == oq.tobytes()
+    assert fe.read_iq("/nonexistent/file.iq")[2] == 0
+
+
+def test_compiled_reference_writer_and_readers_round_trip(tmp_path):
+    """writeRawIQfile, then readRawIQfile of what it wrote; the same payload under a .c2 header through readC2file, at
+    full length and cut short.  The oracle's reader and the C ABI's readers and writer give the same bytes."""
+    fe = _front()
+    L = w.lib()
+    rng = np.random.default_rng(3)
+    I = rng.normal(0, 0.1, 45000).astype(np.float32); Q = rng.normal(0, 0.1, 45000).astype(np.float32)
+    I[7] = 0.0; Q[7] = -0.0                                         # the sign flip of a zero is kept on disk
+    pr, pg = tmp_path / "ref.iq", tmp_path / "abi.iq"
+    assert fe.write_iq(I, Q, str(pr)) == 45000
+    assert L.wspr_write_iq_file(str(pg).encode(), ol.ptr(I), ol.ptr(Q)) == 45000
+    disk = pr.read_bytes()
+    assert disk == pg.read_bytes() and len(disk) == 8 * 45000
+    raw = np.frombuffer(disk, np.float32)
+    assert raw[0::2].tobytes() == I.tobytes() and raw[1::2].tobytes() == (-Q).tobytes()
+    ri, rq, rn = fe.read_iq(str(pr))
+    oi, oq, on = ol.read_iq_file(str(pr))
+    gi = np.zeros(45000, np.float32); gq = np.zeros(45000, np.float32)
+    assert rn == on == L.wspr_read_iq_file(str(pr).encode(), ol.ptr(gi), ol.ptr(gq)) == 45000
+    assert ri.tobytes() == oi.tobytes() == gi.tobytes() and rq.tobytes() == oq.tobytes() == gq.tobytes()
+    L.wspr_read_c2_file.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    for nfloat in (90000, 80000, 2 * 1023 + 1):
+        c2 = tmp_path / ("x%d.c2" % nfloat)
+        with open(c2, "wb") as f:
+            f.write(b"150426_0918.c2" + struct.pack("<i", 2) + struct.pack("<d", 14095600.0))
+            raw[:nfloat].tofile(f)
+        ri, rq, rn = fe.read_c2(str(c2))
+        oi = np.zeros(45000, np.float32); oq = np.zeros(45000, np.float32)
+        on = ol.lib().orc_iq_from_interleaved(ol.ptr(raw), C.c_int(nfloat), ol.ptr(oi), ol.ptr(oq))
+        dial = C.c_double()
+        gi = np.zeros(45000, np.float32); gq = np.zeros(45000, np.float32)
+        gn = L.wspr_read_c2_file(str(c2).encode(), ol.ptr(gi), ol.ptr(gq), C.byref(dial))
+        assert rn == on == gn == nfloat // 2 and dial.value == 14095600.0
+        assert ri.tobytes() == oi.tobytes() == gi.tobytes() and rq.tobytes() == oq.tobytes() == gq.tobytes()
 
 
 def test_spot_line_format_matches_reference_report():

@@ -194,8 +194,8 @@ def test_config5_full_size_raw_segments_through_k0_and_decode(env):
 def test_config5_64_distinct_raw_segments_in_waves(env):
     """configs[4] beyond three segments (verdict of round 4): 64 DISTINCT full-size raw segments (36.9 GB resident), through
     the front end in four waves of 16 into the rows of an IQ ring -- the shape bench.py --config 5 runs -- and one decoder
-    call over the 64 rows.  Every row's decimated IQ bit-exact vs the oracle front end (parity UNPINNED for this function:
-    oracle/orc_frontend.c has no reference-held fixture), every row's spots equal the oracle decoder's field for field."""
+    call over the 64 rows.  Every row's decimated IQ bit-exact vs the oracle front end (itself pinned to the
+    reference's compiled callback, tests/test_reference_pin_frontend.py), every row's spots equal the oracle decoder's field for field."""
     torch, bench, w, dev = env
     from concurrent.futures import ThreadPoolExecutor
     RAW = bench.RAW_BYTES

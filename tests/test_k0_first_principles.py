@@ -1,9 +1,9 @@
 """An independent derivation of the receiver front end (rtlsdr_wsprd.c:126-244), written from the reference source alone
 and WITHOUT consulting oracle/orc_frontend.c, in NumPy: closed forms instead of the sample loop.
 
-The decimator's oracle is "parity unpinned" (the callback is a `static` function of a translation unit that needs
-<rtl-sdr.h>, libusb and libcurl, and the reference holds no decimator fixture -- DESIGN.md section 2).  This test does
-not change that; it makes a shared misreading of the source by oracle and kernel much less likely: a third reading,
+The decimator's oracle is pinned to the reference's compiled callback (tests/test_reference_pin_frontend.py, DESIGN.md
+section 2); this test was written before that pin existed and stays as a reading that needs no compiled reference.  It
+makes a shared misreading of the source by oracle and kernel much less likely: a third reading,
 structured differently (whole-array integer prefix sums modulo 2^32, combs in closed form, the FIR as 33 array
 operations in tap order), must give the same bits as both.
 
