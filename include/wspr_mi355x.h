@@ -364,7 +364,10 @@ void subtract_signal2(float *id, float *qd, long np, float f0, int shift, float 
  * start (candidate lists, re-ranking), [18] wave building, [19] fine search + first rung (launches, lists, gates),
  * [20] ladder, [21] bookkeeping (unpack, re-encode, de-dup), [22] subtraction launches, [23] result hand-over;
  * then [24] decoded messages looked up in the calling thread's message cache (what a 50-bit message unpacks and
- * re-encodes to, computed once per thread and message) and [25] how many of them it answered.
+ * re-encodes to, computed once per thread and message) and [25] how many of them it answered;
+ * then the ordered-statistics rescue stage (wspr_set_osd_depth(); all zero while it is off), summed like the counts:
+ * [26] the stage's wall time, milliseconds (K9 and its round trips), [27] soft-symbol vectors it tried, [28] how many
+ * of its results the "heard before" gate let through.
  * Returns the number of values written (<= capacity). */
 int wspr_last_timings(double *ms, int capacity);
 /* Worker threads of the library's host pools alive in this process (the threads that call into the library are
@@ -443,6 +446,40 @@ int wspr_set_fano_device_mode(int mode);
 #define WSPR_ARITH_EXACT      0
 #define WSPR_ARITH_CONTRACTED 1
 int wspr_set_arithmetic(int mode);
+/* Ordered-statistics decoding (OSD), an opt-in second chance for candidates on which every Fano attempt failed --
+ * what current WSJT-X wsprd offers as -o; the reference (v0.5.6) predates it, so there is no reference behaviour to
+ * match and the definition is this library's own (rtlsdr-wsprd_amd/csrc/kernels/osd.h; kernel K9):
+ *   the 162 soft symbols s[i] are deinterleaved; h[i] = (s[i] >= 128), r[i] = |2 s[i] - 255|; the positions are sorted
+ *   by r descending (ties: lower index) and, in that order, the first 50 whose columns of the code's generator are
+ *   linearly independent form the most reliable basis; the codeword c_0 that agrees with h on the basis and every
+ *   c_0 + (up to `depth` rows of the generator reduced to that basis) is tried -- 1, 51, 1 276, 20 876 codewords for
+ *   depth 0..3 -- and the one with the smallest sum of r over the positions where it differs from h wins (ties: fewer
+ *   rows, then the lexicographically smaller set of rows).
+ * wspr_osd_batch_device(): that decode for n vectors of 162 soft symbols in transmission (interleaved) order, as
+ * wspr_fano_batch_device_wave() takes them.  Per vector: data[11] = the winner's 50 message bits as fano() leaves its
+ * decdata (the other bits zero), dist = its cost, nhard = the positions where it differs from h, order = the rows
+ * added to c_0.  Returns 0; -1 without a usable device, for a depth outside 0..3 or n < 0; n == 0 does nothing.
+ *
+ * wspr_set_osd_depth(): process-wide, -1 = off (the default), 0..3 = the depth of a rescue stage in every decode call
+ * (read once per call, on entry, like wspr_set_arithmetic(); a WSPR_HASH_REVISIT call must run under the depth of the
+ * call it completes).  Returns the previous value; any other argument changes nothing and returns -2.  While it is on:
+ *   - the Fano budget split (wspr_set_fano_fast_budget) is off for the call -- results never depended on it;
+ *   - a candidate that was worth the jitter ladder, decoded on none of its rungs and whose FIRST soft-symbol vector
+ *     passed the sync/rms gate of wsprd.c:758 has that vector decoded as above;
+ *   - the result counts only if it is a type-1 message (CALL GRID dBm) whose callsign the hash memory already holds at
+ *     that callsign's slot, i.e. a station HEARD BEFORE; otherwise the candidate stays undecoded (no spot, nothing
+ *     stored, nothing subtracted).  An accepted one is a decode like any other -- spot, store, subtraction -- reported
+ *     with jitter 0 and cycles 0: the Fano search never reports fewer than 81 cycles, so cycles == 0 marks an OSD spot.
+ * What to expect: with usehashtable = 0 the hash memory is the call's own and starts empty, so the stage can only
+ * confirm a call that the SAME segment already decoded (a second copy at another frequency, or on a later pass).  The
+ * mode pays with usehashtable = 1 on a receiver that hears the same stations slot after slot: hashtable.txt then
+ * carries the calls from call to call, and within a batch the gate's look-up is ordered exactly like a type-3 look-up
+ * (segment k sees what segments < k stored; wspr_decode_batch_hashed() and rtlsdr-wsprd_amd/dist.py likewise).
+ * An unknown call is never reported by this stage; a known call can be reported falsely only if noise lands on a
+ * codeword of one of the few hundred stored calls (tools/osd_sensitivity.py measures both). */
+int wspr_osd_batch_device(const unsigned char *symbols, int n, int depth, unsigned char *data, unsigned *dist,
+                          unsigned *nhard, unsigned *order);
+int wspr_set_osd_depth(int depth);
 /* Library / device description, e.g. for bench logs. */
 const char *wspr_mi355x_version(void);
 int wspr_device_ready(void);        /* 1 if a HIP device and the kernels are usable */

@@ -122,6 +122,10 @@ def _bind(path):
     L.wspr_set_fano_fast_budget.restype = C.c_uint
     L.wspr_set_arithmetic.argtypes = [C.c_int]
     L.wspr_set_arithmetic.restype = C.c_int
+    L.wspr_set_osd_depth.argtypes = [C.c_int]
+    L.wspr_set_osd_depth.restype = C.c_int
+    L.wspr_osd_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wspr_osd_batch_device.restype = C.c_int
     L.wspr_synth_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int,
                                           C.c_void_p, C.c_void_p]
     L.wspr_synth_batch_device.restype = C.c_int
@@ -192,6 +196,26 @@ def wspr_set_arithmetic(mode, library=None):
     WSPR_ARITH_CONTRACTED.  Returns the previous mode, or -1 (nothing changed) for any other value.  The product and
     the lab library each keep their own setting: `library` (default: lib()) is the one set."""
     return (library or lib()).wspr_set_arithmetic(int(mode))
+
+
+def set_osd_depth(depth, library=None):
+    """wspr_set_osd_depth() of include/wspr_mi355x.h: -1 switches the ordered-statistics rescue stage off (the default),
+    0..3 set its depth for every later decode call.  Returns the previous value, or -2 (nothing changed) for any other
+    argument.  Like the arithmetic mode, the product and the lab library each keep their own setting."""
+    return (library or lib()).wspr_set_osd_depth(int(depth))
+
+
+def osd_batch(symbols, depth, library=None):
+    """wspr_osd_batch_device(): ordered-statistics decoding of n vectors of 162 soft symbols (uint8 [n, 162], transmission
+    order).  Returns (data uint8 [n, 11], dist, nhard, order as uint32 [n]); raises if the library refuses the call."""
+    sym = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, NSYM)
+    n = sym.shape[0]
+    data = np.zeros((n, 11), np.uint8)
+    dist, nhard, order = (np.zeros(n, np.uint32) for _ in range(3))
+    rc = (library or lib()).wspr_osd_batch_device(_ptr(sym), n, int(depth), _ptr(data), _ptr(dist), _ptr(nhard), _ptr(order))
+    if rc != 0:
+        raise RuntimeError("wspr_osd_batch_device failed (rc %d: depth outside 0..3, or no usable HIP device)" % rc)
+    return data, dist, nhard, order
 
 
 def get_wspr_channel_symbols(message):
@@ -336,7 +360,8 @@ TIMING_NAMES = (
     "total_ms", "fano_calls", "fano_timeouts", "fano_cycles", "candidates_refined", "gpu_waves",
     "fano_left_to_device", "segments_redecoded", "candidates_consumed", "subtractions",
     "cpu_ms_call", "cpu_ms_pass_start", "cpu_ms_build_wave", "cpu_ms_refine", "cpu_ms_ladder", "cpu_ms_books",
-    "cpu_ms_subtract", "cpu_ms_finish", "message_cache_lookups", "message_cache_hits")
+    "cpu_ms_subtract", "cpu_ms_finish", "message_cache_lookups", "message_cache_hits",
+    "osd_ms", "osd_vectors", "osd_spots")
 
 
 def last_timings():

@@ -5,6 +5,7 @@
 #include <exception>
 
 #include "wspr_capi_impl.h"
+#include "../kernels/osd.h"
 
 using wspr::Context;
 using namespace wspr::capi;
@@ -73,6 +74,21 @@ int wspr_fano_batch_device_wave(const unsigned char* symbols, int n, unsigned ma
     try {
         return Context::get().fano_batch(symbols, n, maxcycles, ret, cycles, metric, maxnp, data, steps);
     } catch (const std::exception& e) { return fail("wspr_fano_batch_device_wave", e); }
+}
+
+int wspr_set_osd_depth(int depth) {
+    if (depth < -1 || depth > wspr::osd::kMaxDepth) return -2;
+    return wspr::osd_depth_setting().exchange(depth);
+}
+
+int wspr_osd_batch_device(const unsigned char* symbols, int n, int depth, unsigned char* data, unsigned* dist,
+                          unsigned* nhard, unsigned* order) {
+    if (depth < 0 || depth > wspr::osd::kMaxDepth || n < 0) return -1;
+    if (n == 0) return 0;
+    LaneTurn lane_turn;
+    try {
+        return Context::get().osd_batch(symbols, n, depth, data, dist, nhard, order);
+    } catch (const std::exception& e) { return fail("wspr_osd_batch_device", e); }
 }
 
 int wspr_host_pool_workers(void) { return wspr::pool_workers_alive().load(); }

@@ -46,7 +46,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
     const int nslots = (nseg >= 128) ? Context::slot_cap() : 1;
     Context::note_slots_used(nslots);
     Context& c0 = Context::get();
-    const int dev = c0.device(), lane = Context::lane(), arith = wspr::call_arith();
+    const int dev = c0.device(), lane = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth();
     struct Share { int lo, hi; };
     std::vector<Share> share(nslots);
     for (int g = 0; g < nslots; ++g) share[g] = {(int)((long)nseg * g / nslots), (int)((long)nseg * (g + 1) / nslots)};
@@ -60,6 +60,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
             th.emplace_back([&, g] {
                 try {
                     wspr::ArithScope call_mode(arith);
+                    wspr::OsdScope call_osd(osd_depth);
                     if (hipSetDevice(dev) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
                     Context::bind_lane(lane);
                     fn(g, Context::slot(g));
@@ -163,13 +164,15 @@ int decode_hashed(int nseg, int samples, const decoder_options& options, decoder
     // same segments, samples and slot layout (wspr_set_thread_slots / a node-level share in between change the shares)
     const int nslots_now = (nseg >= 128) ? Context::slot_cap() : 1;
     if (revisit && !(t_hash && t_hash->valid && (int)t_hash->log.size() == nseg && t_hash->seg0 == seg_index0 &&
-                     t_hash->samples == samples && t_hash->nslots == nslots_now && t_hash->arith == wspr::call_arith()))
+                     t_hash->samples == samples && t_hash->nslots == nslots_now && t_hash->arith == wspr::call_arith() &&
+                     t_hash->osd_depth == wspr::call_osd_depth()))
         throw std::runtime_error("WSPR_HASH_REVISIT without a matching, completed previous call on this thread");
     if (!revisit) {
         t_hash.reset(new wspr::HashBatch);
         t_hash->load_file();
         t_hash->seg0 = seg_index0;
         t_hash->arith = wspr::call_arith();
+        t_hash->osd_depth = wspr::call_osd_depth();
         t_hash->resize(nseg);
     }
     wspr::HashBatch& hb = *t_hash;

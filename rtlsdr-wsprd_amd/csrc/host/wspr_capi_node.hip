@@ -76,7 +76,8 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
         return wspr_decode_batch(idat, qdat, nseg, samples, seg_stride, options, decodes, max_results, n_results, 0);
     NodeShareGuard share(ndevices);
     wspr::ArithScope call_mode;
-    const int lane0 = Context::lane(), arith = wspr::call_arith();
+    wspr::OsdScope call_osd;
+    const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth();
     int home = 0;
     (void)hipGetDevice(&home);
     std::vector<int> rcs(ndevices, 0);
@@ -87,6 +88,7 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
         if (hi <= lo) continue;
         th.emplace_back([=, &rcs] {
             wspr::ArithScope worker_mode(arith);
+            wspr::OsdScope worker_osd(osd_depth);
             if (hipSetDevice(k % count) != hipSuccess) {
                 rcs[k] = -1;
                 for (int s = lo; s < hi; ++s) n_results[s] = 0;
@@ -140,7 +142,8 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
     }
     NodeShareGuard share(ndevices);
     wspr::ArithScope call_mode;
-    const int lane0 = Context::lane(), arith = wspr::call_arith();
+    wspr::OsdScope call_osd;
+    const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth();
     std::vector<int> rcs(ndevices, 0);
     std::vector<std::thread> th;
     for (int k = 0; k < ndevices; ++k) {
@@ -149,6 +152,7 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
         if (hi <= lo) continue;
         th.emplace_back([=, &rcs] {
             wspr::ArithScope worker_mode(arith);
+            wspr::OsdScope worker_osd(osd_depth);
             const int dev = k % count;
             if (hipSetDevice(dev) != hipSuccess) { rcs[k] = -1; return; }
             Context::bind_lane(lane0 + k / count);

@@ -97,6 +97,17 @@ Context::Context(int nslots) : d(new Impl) {
         for (int i = 0; i < 256; ++i) metric0[i] = (short)default_metrics().tab[0][i];
         upload(d->t_metric0.need(sizeof metric0), metric0, sizeof metric0, d->stream);
     }
+    {
+        // K9's generator: row j = the encoder's first 162 outputs for message bit j alone (kernels/osd.h)
+        static uint32_t gen[osd::kK * osd::kRowWords];
+        for (int j = 0; j < osd::kK; ++j) {
+            unsigned char data[11] = {0}, code[176];
+            data[j >> 3] = (unsigned char)(0x80u >> (j & 7));
+            conv_encode(code, data, 11);
+            osd::pack_generator_row(code, j, gen + j * osd::kRowWords);
+        }
+        upload(d->t_osdgen.need(sizeof gen), gen, sizeof gen, d->stream);
+    }
     HIP_OK(hipStreamSynchronize(d->stream));
     d->tab.window = d->t_window.as<float>();
     d->tab.twiddle = d->t_twiddle.as<float2>();

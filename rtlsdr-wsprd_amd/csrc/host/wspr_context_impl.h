@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "wspr_message.h"
+#include "../kernels/osd.h"
 
 namespace wspr {
 
@@ -238,9 +239,9 @@ struct Context::Impl {
     int fe_cus = 0;                    // CUs the mask of fe_stream admits (0: fe_stream not in use)
     int device = 0;
     DeviceTables tab{};
-    DevBuf t_window, t_twiddle, t_sync, t_lpf, t_part, t_jitter, t_metric0;
+    DevBuf t_window, t_twiddle, t_sync, t_lpf, t_part, t_jitter, t_metric0, t_osdgen;
     DevBuf iqI, iqQ, ps, cand, npk, noise, smspec, seglist, items, syncbuf, symbuf, rmsbuf, jobs, subscratch,
-        nvalid, decscratch, tabs, pw, pwfreq, lists, scrsync, psavg, densein, fz_sym, fz_off, fz_ret, fz_cyc, fz_met, fz_max, fz_dat, fz_steps, fz_pool, streamraw, streamstate,
+        nvalid, decscratch, tabs, pw, pwfreq, lists, scrsync, psavg, densein, fz_sym, fz_off, fz_ret, fz_cyc, fz_met, fz_max, fz_dat, fz_steps, fz_pool, osd_out, streamraw, streamstate,
         synthtx, synthoff, synthfirst, synthckpt, synthrows;   // K8: transmission list, offsets, first indices, phase checkpoints; wspr_selftest()'s rows
     PinBuf h_npk, h_cand, h_items, h_sync, h_sym, h_rms, h_jobs, h_jobs2, h_seglist, h_misc, h_lists;
     // host-buffer entry (wspr_decode_batch: the reference's calling convention, wsprd.h:106-111): pageable caller rows
@@ -248,6 +249,7 @@ struct Context::Impl {
     // so that the host's gather of chunk k+1 runs under the DMA of chunk k and every DMA is one contiguous copy
     PinBuf h_fz;                     // K6w's results on their way to the host (a copy into pageable memory would make
                                      // the runtime wait for the search itself, on a CPU)
+    PinBuf h_osd;                    // K9's results on their way to the host
     PinBuf h_stage[2];
     PinBuf h_streamraw, h_streamstate, h_streamout;   // many receivers' callbacks at once (decimate_stream_many)
     hipEvent_t ev_stage[2] = {nullptr, nullptr};

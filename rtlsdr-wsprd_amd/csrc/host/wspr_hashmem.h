@@ -45,6 +45,7 @@ struct HashBatch {
     bool valid = false;
     int nslots = 0, samples = 0;
     int arith = 0;                                  // wspr_set_arithmetic() mode of the call (a revisit must match it)
+    int osd_depth = -1;                             // wspr_set_osd_depth() of the call (a revisit must match it too)
 
     HashBatch();
     void load_file();                               // hashtable.txt of the working directory (wsprd.c:481-494)

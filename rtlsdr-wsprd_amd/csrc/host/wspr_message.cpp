@@ -457,6 +457,21 @@ int unpack_message(const signed char* msg, HashTable& tab, char* call_loc_pow,
     return noprint;
 }
 
+bool osd_accept(const unsigned char* decdata, HashTable& tab) {
+    signed char msg[11];
+    for (int k = 0; k < 11; ++k) msg[k] = (signed char)decdata[k];
+    int32_t n1, n2;
+    unpack_50bits(msg, &n1, &n2);
+    char callsign[13] = {0}, grid[5] = {0};
+    if (!unpack_callsign(n1, callsign) || !unpack_grid(n2, grid)) return false;
+    const int ntype = (n2 & 127) - 64;
+    if (ntype < 0 || ntype > 62 || !legal_power(ntype)) return false;      // type 1 only (unpack_message above)
+    callsign[12] = '\0';
+    const size_t cl = std::strlen(callsign);
+    if (cl == 0) return false;
+    return std::strcmp(tab.call_at((int)nhash15(callsign, cl, 146u)), callsign) == 0;
+}
+
 // ---------------------------------------------------------------- channel symbols
 namespace {
 // encode() + interleave() + "2 * bit + sync" (wsprsim_utils.c:302-309) of the 11 packed bytes.  Both the convolutional

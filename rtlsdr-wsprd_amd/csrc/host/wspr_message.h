@@ -87,5 +87,9 @@ int unpack_message(const signed char* msg, char* hashtab, char* loctab, char* ca
                    char* call, char* loc, char* pwr, char* callsign);
 int channel_symbols(const char* text, HashTable& tab, unsigned char* symbols);
 int channel_symbols(const char* text, char* hashtab, char* loctab, unsigned char* symbols);
+// The "heard before" gate of an ordered-statistics (OSD) decode, wspr_set_osd_depth(): true when decdata (11 bytes as
+// the decoder leaves them) is a type-1 message whose callsign is what the hash memory holds at that callsign's slot,
+// tab.call_at(nhash(call, strlen(call), 146)).  Stores nothing; the look-up is an ordinary, logged one.
+bool osd_accept(const unsigned char* decdata, HashTable& tab);
 
 }  // namespace wspr

@@ -43,6 +43,21 @@ struct ArithScope {
     ArithScope& operator=(const ArithScope&) = delete;
 };
 
+// wspr_set_osd_depth(): the process-wide depth of the ordered-statistics rescue stage (-1 off, 0..3).  Read ONCE per
+// call, on entry, and handed to the threads a call starts for itself, exactly as the arithmetic mode above.
+std::atomic<int>& osd_depth_setting();
+int& call_osd_slot();                                     // thread-local: the current call's depth, kOsdUnset outside a call
+constexpr int kOsdUnset = -2;
+inline int call_osd_depth() { const int m = call_osd_slot(); return m == kOsdUnset ? osd_depth_setting().load() : m; }
+struct OsdScope {
+    bool owner;
+    OsdScope() : owner(call_osd_slot() == kOsdUnset) { if (owner) call_osd_slot() = osd_depth_setting().load(); }
+    explicit OsdScope(int depth) : owner(call_osd_slot() == kOsdUnset) { if (owner) call_osd_slot() = depth; }
+    ~OsdScope() { if (owner) call_osd_slot() = kOsdUnset; }
+    OsdScope(const OsdScope&) = delete;
+    OsdScope& operator=(const OsdScope&) = delete;
+};
+
 // The values of wspr_last_timings(), in the order include/wspr_mi355x.h documents (that order is ABI; the Python
 // wrapper's TIMING_NAMES repeats it).  A new value goes at the end, here and in both of those.
 enum TimingSlot : int {
@@ -52,6 +67,7 @@ enum TimingSlot : int {
     kTmCpuMsCall, kTmCpuMsPassStart, kTmCpuMsBuildWave, kTmCpuMsRefine, kTmCpuMsLadder, kTmCpuMsBooks, kTmCpuMsSubtract,
     kTmCpuMsFinish,
     kTmMessageCacheLookups, kTmMessageCacheHits,
+    kTmOsdMs, kTmOsdVectors, kTmOsdSpots,
     kTimingSlots
 };
 // A batch runs on several pipelines at once and each keeps its own values; wspr_last_timings() folds them.  The stage
@@ -59,7 +75,7 @@ enum TimingSlot : int {
 // from it on is SUMMED -- the counts, and the CPU times kTmCpuMs* as well (CPU time spent on different threads adds
 // up; the public header says "summed over the slots").
 constexpr int kTimingFirstSummed = kTmFanoCalls;
-static_assert(kTimingSlots == 26 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
+static_assert(kTimingSlots == 29 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
 
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt
@@ -155,6 +171,12 @@ public:
                    unsigned* metric, unsigned* maxnp, unsigned char* data, unsigned* steps = nullptr);
     int fano_resident(const unsigned char* d_symbols, const int* h_offsets, int n, unsigned maxcycles, int* ret,
                       unsigned* cycles, unsigned char* data);
+    // K9 (k9_osd.hip; the definition in kernels/osd.h) over host vectors, and over vectors already in HBM (vector i at
+    // d_symbols + h_offsets[i] * 162); results on the host: data n*11, dist, nhard, order
+    int osd_batch(const unsigned char* symbols, int n, int depth, unsigned char* data, unsigned* dist, unsigned* nhard,
+                  unsigned* order);
+    int osd_resident(const unsigned char* d_symbols, const int* h_offsets, int n, int depth, unsigned char* data,
+                     unsigned* dist, unsigned* nhard, unsigned* order);
     int bench_decimate(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int iters, double* ms);
     int decimate_device(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int normalise,
                         int* h_nout, DecimState* d_states = nullptr);

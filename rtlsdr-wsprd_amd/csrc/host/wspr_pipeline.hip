@@ -206,6 +206,15 @@ int& call_arith_slot() {
     return m;
 }
 
+std::atomic<int>& osd_depth_setting() {
+    static std::atomic<int> v{-1};
+    return v;
+}
+int& call_osd_slot() {
+    thread_local int m = kOsdUnset;
+    return m;
+}
+
 std::atomic<unsigned>& fano_fast_budget() {
     static std::atomic<unsigned> v{[] { const char* e = getenv("WSPR_FANO_FAST"); return e ? (unsigned)atoi(e) : 10000u; }()};
     return v;
@@ -241,7 +250,9 @@ int Context::decode_resident(int nseg, int samples, const decoder_options& opt, 
     // a traced decode runs every attempt with the full budget where it is first met (nothing provisional)
     // (a shared hash memory keeps the host's full budget too: a provisional failure would log look-ups of a decode
     // that is thrown away)
-    const unsigned fast = (reload && nseg >= 256 && !dev_fano && !trace && !hb) ? std::min(fast_cfg, 10000u) : 0u;
+    // (and so does the ordered-statistics stage: it takes the candidates whose every Fano attempt FAILED, which a
+    // provisional failure is not)
+    const unsigned fast = (reload && nseg >= 256 && !dev_fano && !trace && !hb && call_osd_depth() < 0) ? std::min(fast_cfg, 10000u) : 0u;
     if (trace) memset(trace, 0, (size_t)nseg * sizeof(wspr_trace));
     d->dev_fano = dev_fano;
     std::vector<int> all(nseg);
@@ -306,6 +317,12 @@ struct Context::DecodeRun {
         unsigned char sym0[kNSymD];
     };
     std::vector<ItemTrace> wtrace;
+    // wspr_set_osd_depth() of this call (-1: off), and per item of the current wave: its rung-0 vector passed the
+    // sync/rms gate; its decode is the rescue stage's (decided by the "heard before" gate in keep_books())
+    const int osd_depth = call_osd_depth();
+    std::vector<char> gate0, by_osd;
+    std::atomic<long> n_osd_spots{0};         // candidates the gate let through (bookkeeping runs on the pool's threads)
+    const unsigned char* d_sym0 = nullptr;    // the wave's rung-0 soft symbols in HBM
 
     // one Fano attempt on a soft-symbol vector in transmission order (wsprd.c:759-761)
     int fano_attempt(const unsigned char* tx_sym, unsigned* cycles, unsigned char* data11) const {
@@ -386,6 +403,7 @@ struct Context::DecodeRun {
     std::vector<WaveItem> build_wave(const std::vector<int>& active);
     void refine_and_first_rung(std::vector<WaveItem>& wave);
     void remaining_rungs(std::vector<WaveItem>& wave);
+    void osd_rescue(std::vector<WaveItem>& wave);
     std::vector<SubJob> keep_books(std::vector<WaveItem>& wave);
     void subtract(const std::vector<SubJob>& jobs);
     void finish(const std::vector<int>& active0, int* n_results);
@@ -577,6 +595,11 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
     h_sync = reinterpret_cast<float*>(h_down + o_sync);
     h_rms = reinterpret_cast<float*>(h_down + o_rms);
     h_sym = reinterpret_cast<unsigned char*>(h_down + o_sym);
+    if (osd_depth >= 0) {                                      // the rescue stage needs these after the ladder reused the block
+        this->d_sym0 = d_sym0;
+        gate0.resize(nw);
+        for (int i = 0; i < nw; ++i) gate0[i] = gated(i) ? 1 : 0;
+    }
 
     if (trace)
         for (int i = 0; i < nw; ++i) {
@@ -771,6 +794,33 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
     }
 }
 
+// Ordered-statistics rescue (wspr_set_osd_depth() >= 0): every candidate of the wave that was worth a ladder, whose
+// every Fano attempt failed and whose rung-0 vector passed the sync/rms gate goes through K9, straight from the rung-0
+// symbols in HBM (the ladder's upload only rewrote the head of that block, the items).  The result is provisional: it
+// counts as a decode only if keep_books() finds its callsign in the hash memory (osd_accept()).  cycles == 0 marks it:
+// the Fano search never reports fewer than 81.
+void Context::DecodeRun::osd_rescue(std::vector<WaveItem>& wave) {
+    const int nw = (int)wave.size();
+    by_osd.assign(nw, 0);
+    std::vector<int> att;
+    for (int i = 0; i < nw; ++i)
+        if (wave[i].worth && !wave[i].decoded && gate0[i]) att.push_back(i);
+    if (att.empty()) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int na = (int)att.size();
+    std::vector<unsigned char> dat((size_t)na * 11);
+    std::vector<unsigned> dist(na), nhard(na), order(na);
+    ctx.osd_resident(d_sym0, att.data(), na, osd_depth, dat.data(), dist.data(), nhard.data(), order.data());
+    for (int k = 0; k < na; ++k) {
+        WaveItem& w = wave[att[k]];
+        by_osd[att[k]] = 1;
+        w.decoded = true; w.jitter = 0; w.cycles = 0;
+        memcpy(w.decdata, dat.data() + (size_t)k * 11, 11);
+    }
+    c.t_ms[kTmOsdMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c.t_ms[kTmOsdVectors] += (double)na;
+}
+
 // Host bookkeeping in candidate order (wsprd.c:768-822).  Items of one segment are contiguous in the
 // wave and must be handled in order; different segments are independent -> one pool task per segment.
 // Returns the subtraction jobs of the wave.
@@ -793,6 +843,18 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
         if (stopped[s]) break;
         c.n_kept++;
         if (lockstep) next_cand[s] = w.cand + 1;
+        SegBook& bk = book[s];
+        // the segment's hash memory: its own zeroed tables (the reference's locals, wsprd.c:478-479; every slot written
+        // is noted and cleared again when the batch ends), or its window on the batch's shared memory (usehashtable)
+        FlatHashTable flat(persist ? hashtab_of(s) : nullptr, persist ? loctab_of(s) : nullptr, &bk.dirty);
+        std::unique_ptr<SegHashView> shared((hb && w.worth && w.decoded) ? new SegHashView(hb, hb_off + s) : nullptr);
+        HashTable& tab = shared ? static_cast<HashTable&>(*shared) : (persist ? static_cast<HashTable&>(flat) : static_cast<HashTable&>(bk.hash));
+        // an ordered-statistics decode counts only for a call heard before; decided before anything is stored or traced
+        // (the look-up is logged like a type-3 look-up, so a batch with usehashtable orders it)
+        if (osd_depth >= 0 && by_osd[i] && w.worth && w.decoded) {
+            if (osd_accept(w.decdata, tab)) n_osd_spots++;
+            else w.decoded = false;
+        }
         DevCand& cd = cand[(size_t)s * kMaxCand + w.cand];
         cd.freq = w.fine.freq; cd.shift = w.fine.shift; cd.drift = w.fine.drift; cd.sync = w.fine.sync;
         wspr_cand_trace* tc = nullptr;
@@ -816,12 +878,6 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
         signed char message[12] = {0};
         for (int k = 0; k < 11; ++k) message[k] = (signed char)w.decdata[k];
         char callsign[13] = {0}, call_loc_pow[23] = {0}, call[13] = {0}, loc[7] = {0}, pwr[3] = {0};
-        SegBook& bk = book[s];
-        // the segment's hash memory: its own zeroed tables (the reference's locals, wsprd.c:478-479; every slot written
-        // is noted and cleared again when the batch ends), or its window on the batch's shared memory (usehashtable)
-        FlatHashTable flat(persist ? hashtab_of(s) : nullptr, persist ? loctab_of(s) : nullptr, &bk.dirty);
-        std::unique_ptr<SegHashView> shared(hb ? new SegHashView(hb, hb_off + s) : nullptr);
-        HashTable& tab = hb ? static_cast<HashTable&>(*shared) : (persist ? static_cast<HashTable&>(flat) : static_cast<HashTable&>(bk.hash));
         // (what the bits unpack and re-encode to is computed once per host thread: MessageCache, wspr_hashmem.h)
         MessageCache& mc = MessageCache::of_this_thread();
         const unsigned long mc_hits0 = mc.hits;
@@ -972,12 +1028,14 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
             if (wave.empty()) break;
             { CpuSpan sp(&d->t_ms[kTmCpuMsRefine]); run.refine_and_first_rung(wave); }
             { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.remaining_rungs(wave); }
+            if (run.osd_depth >= 0) { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.osd_rescue(wave); }
             std::vector<SubJob> jobs;
             { CpuSpan sp(&d->t_ms[kTmCpuMsBooks]); jobs = run.keep_books(wave); }
             { CpuSpan sp(&d->t_ms[kTmCpuMsSubtract]); run.subtract(jobs); }
         }
     }
     { CpuSpan sp(&d->t_ms[kTmCpuMsFinish]); run.finish(active0, n_results); }
+    d->t_ms[kTmOsdSpots] += (double)run.n_osd_spots.load();
     guard.armed = false;
     return 0;
 }
@@ -1205,6 +1263,45 @@ int Context::fano_batch(const unsigned char* symbols, int n, unsigned maxcycles,
         }
     }
     return 0;
+}
+
+// K9 over vectors that are already in HBM (the decode loop's rescue stage): vector i is the 162 soft symbols at
+// d_symbols + h_offsets[i] * 162, transmission order.  Results on the host.
+int Context::osd_resident(const unsigned char* d_symbols, const int* h_offsets, int n, int depth, unsigned char* data,
+                          unsigned* dist, unsigned* nhard, unsigned* order) {
+    Impl& c = *d;
+    if (n <= 0) return 0;
+    int* h_off = static_cast<int*>(c.h_misc.need((size_t)n * 4));
+    memcpy(h_off, h_offsets, (size_t)n * 4);
+    int* doff = static_cast<int*>(c.fz_off.need((size_t)n * 4));
+    // one result block [dist | nhard | order | data]: one copy down
+    const size_t o_data = (size_t)n * 12, blk = o_data + (size_t)n * 11;
+    char* dout = static_cast<char*>(c.osd_out.need(blk));
+    char* hout = static_cast<char*>(c.h_osd.need(blk));
+    upload(doff, h_off, (size_t)n * 4, c.stream);
+    launch_osd(d_symbols, doff, n, depth, c.t_osdgen.as<uint32_t>(), reinterpret_cast<unsigned char*>(dout + o_data),
+               reinterpret_cast<unsigned*>(dout), reinterpret_cast<unsigned*>(dout + (size_t)n * 4),
+               reinterpret_cast<unsigned*>(dout + (size_t)n * 8), c.stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(hout, dout, blk, hipMemcpyDeviceToHost, c.stream));
+    sync();
+    memcpy(dist, hout, (size_t)n * 4);
+    memcpy(nhard, hout + (size_t)n * 4, (size_t)n * 4);
+    memcpy(order, hout + (size_t)n * 8, (size_t)n * 4);
+    memcpy(data, hout + o_data, (size_t)n * 11);
+    return 0;
+}
+
+// K9 over n host vectors (wspr_osd_batch_device)
+int Context::osd_batch(const unsigned char* symbols, int n, int depth, unsigned char* data, unsigned* dist,
+                       unsigned* nhard, unsigned* order) {
+    Impl& c = *d;
+    if (n <= 0) return 0;
+    unsigned char* dsym = static_cast<unsigned char*>(c.fz_sym.need((size_t)n * kNSymD));
+    upload(dsym, symbols, (size_t)n * kNSymD, c.stream);
+    std::vector<int> off(n);
+    for (int i = 0; i < n; ++i) off[i] = i;
+    return osd_resident(dsym, off.data(), n, depth, data, dist, nhard, order);
 }
 
 // Device Fano search over vectors that are already in HBM: attempt i is the 162 soft symbols at

@@ -168,6 +168,11 @@ size_t fano_wave_scratch_words(int n);
 void launch_fano_wave(const unsigned char* symbols, const int* offsets, int n, const short* metric0,
                       unsigned maxcycles, int* ret, unsigned* cycles, unsigned* metric, unsigned* maxnp,
                       unsigned char* data, unsigned* steps, uint32_t* scratch, hipStream_t st);
+// K9, ordered-statistics decoding (k9_osd.hip; the definition in osd.h): one wavefront per vector, vector i = the 162 soft
+// symbols at symbols + offsets[i] * 162 (transmission order).  depth 0..3; gen = the 50 generator rows of 7 words
+// (osd::pack_generator_row).  Outputs per vector: data[11], dist, nhard, order.
+void launch_osd(const unsigned char* symbols, const int* offsets, int n, int depth, const uint32_t* gen,
+                unsigned char* data, unsigned* dist, unsigned* nhard, unsigned* order, hipStream_t st);
 // K8, the signal synthesiser (k8_synth.hip; arithmetic in synth_math.h).  SynthTx is wspr_synth_tx of the public header.
 struct SynthTx {
     int32_t seg;
