@@ -367,7 +367,11 @@ void subtract_signal2(float *id, float *qd, long np, float f0, int shift, float 
  * re-encodes to, computed once per thread and message) and [25] how many of them it answered;
  * then the ordered-statistics rescue stage (wspr_set_osd_depth(); all zero while it is off), summed like the counts:
  * [26] the stage's wall time, milliseconds (K9 and its round trips), [27] soft-symbol vectors it tried, [28] how many
- * of its results the "heard before" gate let through.
+ * of its results the "heard before" gate let through;
+ * then the lag pruning of the fine search's full lag scan (drift-free candidates), summed like the counts: [29] candidates
+ * whose losing lags a bounded coarse pass ruled out, [30] the exact single-lag evaluations those candidates took
+ * instead of 33 each, [31] candidates that fell back to the whole scan (too many contenders, or a quantity the bound
+ * does not cover).
  * Returns the number of values written (<= capacity). */
 int wspr_last_timings(double *ms, int capacity);
 /* Worker threads of the library's host pools alive in this process (the threads that call into the library are

@@ -6,6 +6,9 @@
  * switches that select alternative kernels or repeat stages (WSPR_K0_KERNEL, WSPR_K0_RESIDENT, WSPR_K0_CUS,
  * WSPR_K1_FUSED, WSPR_K3_KERNEL, WSPR_K4_LAG, WSPR_K4_FREQ, WSPR_K4_DRIFT, WSPR_REPEAT_LAG / _FREQ / _FANO,
  * WSPR_FANO_WAVE_CAP, WSPR_NODE_VIRTUAL; docs/HISTORY.md section 4 "Switches"), which read as unset in the product.
+ * WSPR_K4_LAG: unset = the lag pruning (a bounded coarse pass names the lags that can still win, exact sums for those only;
+ * its counts are wspr_last_timings() [29]..[31]); "full" = the whole strided scan for every drift-free candidate, as before
+ * the pruning; "tile" = the same on the tiled kernel.
  * tests/ and bench.py load the lab library for these calls and the product library for everything else.
  * ==========================================================================*/
 #ifndef WSPR_MI355X_BENCH_H
@@ -76,7 +79,8 @@ int wspr_stage_candidates(const float *idat, const float *qdat, int nseg, int sa
 int wspr_bench_fft_sync(const void *d_idat, const void *d_qdat, int nseg, int samples,
                         size_t seg_stride, int iters, double *ms);
 /* Times the two fp32-VALU-bound stages on resident data with HIP events on the launch stream: the
- * strongest candidate of every segment through the tiled lag scan (K4 mode 0, reference wsprd.c:709-719)
+ * strongest candidate of every segment through the WHOLE lag scan (K4 mode 0, reference wsprd.c:709-719: all 33 lags of
+ * every candidate on demod_lagsys_kernel, the prescribed arithmetic's roofline -- not the pruned default path)
  * and the fused frequency scan + first ladder rung (wsprd.c:721-758), and one coherent subtraction
  * (K7, wsprd.c:316-413) per segment.  ms must hold 8 doubles: ms[0] = lag scan, ms[1] = subtraction,
  * ms[2] = candidates, ms[3] = subtraction jobs, ms[4] = frequency scan + first rung (milliseconds per

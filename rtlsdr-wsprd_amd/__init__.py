@@ -361,7 +361,7 @@ TIMING_NAMES = (
     "fano_left_to_device", "segments_redecoded", "candidates_consumed", "subtractions",
     "cpu_ms_call", "cpu_ms_pass_start", "cpu_ms_build_wave", "cpu_ms_refine", "cpu_ms_ladder", "cpu_ms_books",
     "cpu_ms_subtract", "cpu_ms_finish", "message_cache_lookups", "message_cache_hits",
-    "osd_ms", "osd_vectors", "osd_spots")
+    "osd_ms", "osd_vectors", "osd_spots", "lag_pruned", "lag_exact_evals", "lag_fallbacks")
 
 
 def last_timings():

@@ -68,6 +68,7 @@ enum TimingSlot : int {
     kTmCpuMsFinish,
     kTmMessageCacheLookups, kTmMessageCacheHits,
     kTmOsdMs, kTmOsdVectors, kTmOsdSpots,
+    kTmLagPruned, kTmLagExactEvals, kTmLagFallbacks,
     kTimingSlots
 };
 // A batch runs on several pipelines at once and each keeps its own values; wspr_last_timings() folds them.  The stage
@@ -75,7 +76,7 @@ enum TimingSlot : int {
 // from it on is SUMMED -- the counts, and the CPU times kTmCpuMs* as well (CPU time spent on different threads adds
 // up; the public header says "summed over the slots").
 constexpr int kTimingFirstSummed = kTmFanoCalls;
-static_assert(kTimingSlots == 29 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
+static_assert(kTimingSlots == 32 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
 
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt

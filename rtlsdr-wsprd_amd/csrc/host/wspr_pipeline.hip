@@ -529,7 +529,9 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
     // One block up, one block down per wave (a small copy costs a blit kernel on the stream and ~10 us of
     // host time each): up = [items | launch lists], down = [items | rung-0 sync | rung-0 rms | rung-0 symbols].
     const size_t up_bytes = (size_t)nw * sizeof(FineState) + (size_t)nw * 2 * 4;
-    const size_t o_sync = (size_t)nw * sizeof(FineState), o_rms = o_sync + (size_t)nw * 4, o_sym = o_rms + (size_t)nw * 4;
+    // (the lag pruning's three counts ride down between the rms values and the symbols)
+    const size_t o_sync = (size_t)nw * sizeof(FineState), o_rms = o_sync + (size_t)nw * 4, o_cnt = o_rms + (size_t)nw * 4;
+    const size_t o_sym = o_cnt + 4 * 4;
     const size_t down_bytes = o_sym + (size_t)nw * kNSymD;
     char* h_up = static_cast<char*>(c.h_items.need(up_bytes));
     char* h_down = static_cast<char*>(c.h_sym.need(std::max(down_bytes, (size_t)nw * kMaxLags * (kNSymD + 8))));
@@ -559,15 +561,17 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
     unsigned char* d_sym0 = reinterpret_cast<unsigned char*>(d_blk + o_sym);
     const float* wi = c.iqI.as<float>();
     const float* wq = c.iqQ.as<float>();
+    LagPrune prune{c.lagprune.need(lag_prune_scratch_bytes(nw)), reinterpret_cast<int*>(d_blk + o_cnt), nullptr};
     {
         Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[kTmDemodMs]);
         upload(d_items, h_items, (size_t)nw * sizeof(FineState), c.stream);
         upload(d_lists, h_lists, (size_t)nw * 2 * 4, c.stream);
-        // mode 0: lag scan (tiled), mode 1: 5 frequencies, mode 2: first rung of the ladder
+        HIP_OK(hipMemsetAsync(prune.counts, 0, 4 * 4, c.stream));
+        // mode 0: lag scan (pruned or tiled), mode 1: 5 frequencies, mode 2: first rung of the ladder
         launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream, call_arith());
         launch_demod_tiled(wi, wq, samples, d_items, nw, d_lists, n_shared, d_lists + nw, n_own, 0, nlag0, lagstep,
-                           0.0f, d_tabs, d_pw, d_sync, nullptr, nullptr, c.tab, c.stream, call_arith());
-        launch_pick_lag(d_items, nw, d_sync, nlag0, lagstep, c.stream);
+                           0.0f, d_tabs, d_pw, d_sync, nullptr, nullptr, c.tab, c.stream, call_arith(), &prune);
+        launch_pick_lag(d_items, nw, d_sync, nlag0, lagstep, c.stream, prune.mask);
         std::vector<FineState> tr_items0;
         if (trace) {                                           // mode-0 result, before the frequency scan refines it
             tr_items0.resize(nw);
@@ -595,6 +599,10 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
     h_sync = reinterpret_cast<float*>(h_down + o_sync);
     h_rms = reinterpret_cast<float*>(h_down + o_rms);
     h_sym = reinterpret_cast<unsigned char*>(h_down + o_sym);
+    {
+        const int* cnt = reinterpret_cast<const int*>(h_down + o_cnt);
+        c.t_ms[kTmLagExactEvals] += cnt[0]; c.t_ms[kTmLagFallbacks] += cnt[1]; c.t_ms[kTmLagPruned] += cnt[2];
+    }
     if (osd_depth >= 0) {                                      // the rescue stage needs these after the ladder reused the block
         this->d_sym0 = d_sym0;
         gate0.resize(nw);

@@ -14,7 +14,10 @@
 //
 // Kernels in this file, by the stage they serve (every one performs demod_kernel's operations per accumulator):
 //   general               demod_kernel                 any mode, any drift; exported sync_and_demodulate()
-//   mode 0, no drift      demod_lagsys_kernel          a strided correlation, samples in registers and handed lane to lane
+//   mode 0, no drift      lag_coarse_kernel + lag_exact_kernel + lag_metric_list_kernel   lag pruning: a bounded coarse pass
+//                                                      names the lags that can still win, exact sums for those only
+//                         demod_lagsys_kernel          the whole scan (fallback, WSPR_K4_LAG=full): a strided correlation,
+//                                                      samples in registers and handed lane to lane
 //   mode 0, drift         demod_drift_kernel           three lags per lane, per-symbol tables in an LDS ring
 //   mode 0 (quick mode), ladder rungs (mode 2, 43 lags)
 //                         phasor_table_kernel + demod_tile_kernel<STEP, shared> + demod_metric_kernel
@@ -714,10 +717,12 @@ __device__ __noinline__ void lagsys_edge_wave(const float* __restrict__ xi, cons
 template <bool kFma>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void demod_lagsys_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
-                         const FineState* __restrict__ items, const int* __restrict__ item_list, int nitems,
-                         const float* __restrict__ tabs, float4* __restrict__ pw_out) {
+                         const FineState* __restrict__ items, const int* __restrict__ item_list, int nitems_host,
+                         const float* __restrict__ tabs, float4* __restrict__ pw_out, const int* __restrict__ nitems_dev) {
     constexpr int nlag = 33;
     const int lane = threadIdx.x;
+    // the lag pruning's fallback list has its length in device memory (the grid is then sized for the longest list)
+    const int nitems = nitems_dev ? *nitems_dev : nitems_host;
     // 1-D grid: first the waves that sum u = 5184 (a candidate per lane: 256 dependent steps of per-lane loads -- at the
     // front of the grid they run under the bulk; as the last workgroup of every 64th candidate, which a 2-D grid made
     // them, the final one trailed the launch by ~0.1 ms), then 27 waves per candidate
@@ -773,9 +778,11 @@ __global__ __launch_bounds__(64)
 void demod_metric_kernel(const float4* __restrict__ pw, const FineState* __restrict__ items, int nitems,
                          int mode, int nlag, float minsync1, float* __restrict__ sync_out,
                          unsigned char* __restrict__ sym_out, float* __restrict__ rms_out,
-                         const unsigned char* __restrict__ pr3) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+                         const unsigned char* __restrict__ pr3, const int* __restrict__ item_list = nullptr) {
+    int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nitems * nlag) return;
+    // with a list (lag pruning: the drifting candidates only) nitems counts its entries
+    if (item_list) idx = item_list[idx / nlag] * nlag + idx % nlag;
     const int item = idx / nlag;
     if (mode == 2 && !(items[item].sync > minsync1)) return;
     const float4* __restrict__ P = pw + (size_t)idx * kNSymD;
@@ -1082,15 +1089,374 @@ void freq_metric_kernel(const float4* __restrict__ pw, FineState* __restrict__ i
     if (lane == 0) rms_out[item] = sqrtf(sq / 162.0f);
 }
 
-// mode 0 epilogue: first lag (in scan order) with the strictly largest metric
+// -----------------------------------------------------------------------------
+// Lag pruning (mode 0: 33 lags, step 8) of a DRIFT-FREE candidate.
+//
+// Mode 0 returns the first-maximum lag and its sync only, so the 32 losing lags need only be PROVED to lose.  The
+// reference reads nothing but the magnitudes p_t = |sum_j x[k + j] tab_t[j]| (wsprd.c:211-218), and a magnitude does not
+// care at which phase the phasor starts: up to rounding and the table's recurrence error
+//     p_t(u) = | sum_{n = 8u}^{8u + 255} z_t[n] |,   z_t[n] = x[k0 + n] e^{-i theta_t n},   u = 32 s + m
+// -- ONE mixed-down stream per tone under a sliding window, which at lag step 8 is the sum of 32 consecutive 8-sample
+// block sums: about 7 % of the scan's arithmetic, none of it bit-exact.
+//   lag_coarse_kernel   a workgroup per candidate forms sync~(m) for the 33 lags that way together with a rigorous
+//                       bound eps(m) on |sync(m) - sync~(m)| (DESIGN.md section 4 derives it term by term); the lags with
+//                       sync~(m) + eps(m) >= max_m' (sync~(m') - eps(m')) are the CONTENDERS -- every first maximum of the
+//                       exact scan is among them.  At most kLpCap contenders: they go to the exact list; more, or a
+//                       quantity the bound cannot vouch for: the candidate goes to the fallback list;
+//   lag_exact_kernel    the reference's 256-tap sums of ONE (candidate, lag) per workgroup, lane = symbol;
+//   demod_lagsys_kernel the whole strided scan for the fallback list (its count read from device memory);
+//   lag_metric_list_kernel   folds the (candidate, lag) rows those two wrote; pick_lag_kernel reads contenders only.
+// Lists and counts live in device memory and the follow-up grids are sized for the worst case (surplus workgroups
+// leave at once), so the wave needs no host wait in between.
+constexpr int kLpLags = 33;
+constexpr int kLpCap = 4;                           // contenders a pruned candidate may have
+constexpr int kCoSyms = 27;                         // symbols per chunk of the coarse pass; 6 chunks
+constexpr int kCoChunks = kNSymD / kCoSyms;
+constexpr int kCoThreads = 256;
+constexpr int kCoOut = 32 * kCoSyms;                // window sums per chunk (+ one: lag 32 of its last symbol)
+constexpr int kCoWork = kCoOut / 8 + 1;             // threads per tone pair that form window sums, eight consecutive ones each
+constexpr int kCoBlocks = kCoOut + 40;              // block sums a chunk stages
+constexpr int kCoPitch = 1024;                      // floats per staged array: index v + v / 8 (stride 9 per thread)
+static_assert(kCoChunks * kCoSyms == kNSymD && 2 * kCoWork <= kCoThreads && kCoBlocks + kCoBlocks / 8 < kCoPitch, "coarse tiling");
+constexpr int kCoRed = 19;                          // per-thread partials: totp and ss of 8 lags, of lag 32, and T
+static_assert(kCoThreads * kCoRed <= 8 * kCoPitch, "the partials reuse the block sums' memory");
+
+__device__ __forceinline__ int co_idx(int v) { return v + (v >> 3); }
+__device__ __forceinline__ double2 cmul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
+
+// The constants of eps(m); one line each in DESIGN.md section 4 ("The bound of the lag pruning")
+constexpr double kLpU = 5.9604644775390625e-8;                         // 2^-24
+constexpr double kLpGammaRef = 514 * kLpU / (1 - 514 * kLpU);          // (a) the reference's serial sum: 514 roundings
+constexpr double kLpCoarse = 64 * kLpU;                                // (c) the coarse pass' own rounding
+constexpr double kLpTInflate = 1 + 256 * kLpU;                         // T~ is itself a rounded sum of positive terms
+constexpr double kLpGammaFold = 648 * kLpU / (1 - 648 * kLpU) + 700 * kLpU / (1 - 700 * kLpU);   // (d) both folds
+constexpr double kLpAbs = 1e-15;                                       // underflow in squares, roots and products
+constexpr double kLpTotpFloor = 1e-9, kLpTCeil = 1e18;                 // outside: the standard model does not hold
+
+__global__ __launch_bounds__(kCoThreads)
+void lag_coarse_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
+                       const FineState* __restrict__ items, const int* __restrict__ item_list, int nitems,
+                       const float* __restrict__ tabs, const unsigned char* __restrict__ pr3, float* __restrict__ sync_out,
+                       int* __restrict__ counts, int* __restrict__ exact_list, int* __restrict__ fb_list,
+                       unsigned long long* __restrict__ mask_out) {
+    __shared__ double2 e3d[4][8], e2d[4][32], ead[4][16], ebd[4][11];      // e^{i theta n}: n = j, 8 j, 256 j, 4096 j
+    __shared__ float2 e3f[4][8], e2f[4][32], e1f[4][164];                  // in float: n = j, 8 j, 256 j
+    __shared__ float Bs[8][kCoPitch];                                      // block sums: real parts of the 4 tones, imaginary parts
+    float (*Bre)[kCoPitch] = Bs, (*Bim)[kCoPitch] = Bs + 4;
+    __shared__ float tedge[64];
+    __shared__ float dmax_s[kCoThreads];
+    __shared__ float sy_s[kLpLags], ep_s[kLpLags];
+    __shared__ int bad_s[kLpLags];
+    __shared__ unsigned long long mask_s;
+    __shared__ int base_s;
+    // candidates that follow each other in the list (the same segment's) go to the same XCD, behind one L2
+    const int per_xcd = (nitems + 7) >> 3;
+    const int pos = ((int)blockIdx.x & 7) * per_xcd + ((int)blockIdx.x >> 3);
+    if (((int)blockIdx.x >> 3) >= per_xcd || pos >= nitems) return;
+    const int item = item_list[pos], tid = threadIdx.x;
+    const FineState st = items[item];
+    const float* __restrict__ xi = dI + (size_t)st.seg * kIqStride;
+    const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
+    const int k0 = st.shift_coarse - 128;
+    const float4* __restrict__ gtab = reinterpret_cast<const float4*>(tabs) + (size_t)st.pad * 512;
+
+    // theta_t: the float phasor_table_kernel seeds the table with, widened; theta * n is exact in double (24 + 16 bits)
+    for (int e = tid; e < 4 * 67; e += kCoThreads) {
+        const int t = e / 67, i = e - 67 * t;
+        const double theta = (double)tone_dphi(st.freq_coarse, st.drift, 0, t);
+        const double n = i < 8 ? i : i < 40 ? 8 * (i - 8) : i < 56 ? 256 * (i - 40) : 4096 * (i - 56);
+        double sn, cs;
+        sincos(theta * n, &sn, &cs);
+        const double2 v = make_double2(cs, sn);
+        if (i < 8) e3d[t][i] = v; else if (i < 40) e2d[t][i - 8] = v; else if (i < 56) ead[t][i - 40] = v; else ebd[t][i - 56] = v;
+    }
+    __syncthreads();
+    for (int e = tid; e < 4 * 204; e += kCoThreads) {
+        const int t = e / 204, i = e - 204 * t;
+        if (i < 8) e3f[t][i] = make_float2((float)e3d[t][i].x, (float)e3d[t][i].y);
+        else if (i < 40) e2f[t][i - 8] = make_float2((float)e2d[t][i - 8].x, (float)e2d[t][i - 8].y);
+        else {
+            const int w = i - 40;
+            const double2 v = cmul(ead[t][w & 15], ebd[t][w >> 4]);
+            e1f[t][w] = make_float2((float)v.x, (float)v.y);
+        }
+    }
+    // (b) delta_tab: the table's largest distance from the ideal phasor, measured on the table the exact sums read
+    float dmax = 0.0f;
+    for (int j = tid; j < kSps; j += kCoThreads) {
+        const float4 c4 = gtab[2 * j], s4 = gtab[2 * j + 1];
+        const float tc[4] = {c4.x, c4.y, c4.z, c4.w}, ts[4] = {s4.x, s4.y, s4.z, s4.w};
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const double2 id = cmul(e3d[t][j & 7], e2d[t][j >> 3]);
+            const double dc = (double)tc[t] - id.x, ds = (double)ts[t] - id.y;
+            const float d = (float)(sqrt(dc * dc + ds * ds) * (1 + 1e-6));
+            dmax = (d > dmax || d != d) ? d : dmax;                    // a NaN in the table stays
+        }
+    }
+    dmax_s[tid] = dmax;
+    if (tid < 64) tedge[tid] = 0.0f;
+
+    float acc_tp[8], acc_ss[8], acc_tp32 = 0.0f, acc_ss32 = 0.0f, tall = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 8; ++r) acc_tp[r] = acc_ss[r] = 0.0f;
+    for (int c = 0; c < kCoChunks; ++c) {
+        const int s0 = kCoSyms * c, v0 = 32 * s0;
+        __syncthreads();                                               // tables ready / the previous chunk consumed
+        // block sums B_t[v] = e^{-i theta_t 8 v} sum_j x[k0 + 8 v + j] e^{-i theta_t j}, one block per thread and round
+#pragma unroll 2
+        for (int v = tid; v < kCoBlocks; v += kCoThreads) {
+            const int gv = v0 + v, k = k0 + 8 * gv;
+            float xI[8], xQ[8], tb = 0.0f;
+            if (k > 0 && k + 8 <= np) {                                // the whole block inside the record: 16-byte loads
+                typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+                const f4u a = *reinterpret_cast<const f4u*>(xi + k), b = *reinterpret_cast<const f4u*>(xi + k + 4);
+                const f4u c4 = *reinterpret_cast<const f4u*>(xq + k), d = *reinterpret_cast<const f4u*>(xq + k + 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { xI[j] = a[j]; xI[4 + j] = b[j]; xQ[j] = c4[j]; xQ[4 + j] = d[j]; }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    xI[j] = sys_load_checked(xi, k + j, np);           // wsprd.c:199: 0 < k < np
+                    xQ[j] = sys_load_checked(xq, k + j, np);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 8; ++j) tb += fabsf(xI[j]) + fabsf(xQ[j]);
+            // T: every block once (chunks overlap by 40 blocks); the first and last 32 blocks belong to some lags only
+            if (v < kCoOut || (c == kCoChunks - 1 && v < kCoOut + 32)) {
+                if (gv < 32) tedge[gv] = tb;
+                else if (gv >= 32 * kNSymD) tedge[32 + gv - 32 * kNSymD] = tb;
+                else tall += tb;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; ++t) {
+                float re = 0.0f, im = 0.0f;
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const float2 e = e3f[t][j];
+                    re = __builtin_fmaf(xI[j], e.x, __builtin_fmaf(xQ[j], e.y, re));
+                    im = __builtin_fmaf(xQ[j], e.x, __builtin_fmaf(-xI[j], e.y, im));
+                }
+                const float2 a1 = e1f[t][gv >> 5], a2 = e2f[t][gv & 31];
+                const float ca = a1.x * a2.x - a1.y * a2.y, sa = a1.x * a2.y + a1.y * a2.x;
+                Bre[t][co_idx(v)] = re * ca + im * sa;
+                Bim[t][co_idx(v)] = im * ca - re * sa;
+            }
+        }
+        __syncthreads();
+        // window sums W(u) = B[u] + .. + B[u + 31] for eight consecutive u: the 25 blocks they share, then each one's own
+        if (tid < 2 * kCoWork) {
+            // thread = (tone pair, g): tones (0, 1) or (2, 3) of the window sums 8 g .. 8 g + 7
+            const int pair = tid >= kCoWork ? 1 : 0, g = tid - kCoWork * pair;
+            float tp[8], cm[8];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) tp[r] = cm[r] = 0.0f;
+#pragma unroll 1
+            for (int t = 2 * pair; t < 2 * pair + 2; ++t) {
+                float w[2][8];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const float* __restrict__ b = (h ? Bim[t] : Bre[t]) + 9 * g;        // co_idx(8 g + i) = 9 g + i + i / 8
+                    float mid = b[co_idx(7)];
+#pragma unroll
+                    for (int i = 8; i < 32; ++i) mid += b[co_idx(i)];
+                    float suf = 0.0f, pre = 0.0f, sfx[8], pfx[8];
+                    sfx[7] = 0.0f;
+#pragma unroll
+                    for (int r = 6; r >= 0; --r) { suf += b[co_idx(r)]; sfx[r] = suf; }
+                    pfx[0] = 0.0f;
+#pragma unroll
+                    for (int r = 1; r < 8; ++r) { pre += b[co_idx(31 + r)]; pfx[r] = pre; }
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) w[h][r] = (sfx[r] + mid) + pfx[r];
+                }
+#pragma unroll
+                for (int r = 0; r < 8; ++r) {
+                    const float p = __builtin_amdgcn_sqrtf(w[0][r] * w[0][r] + w[1][r] * w[1][r]);      // v_sqrt_f32: one ulp, in (c)
+                    tp[r] += p;
+                    cm[r] += (t & 1) ? p : -p;                          // (p1 + p3) - (p0 + p2), wsprd.c:216
+                }
+            }
+            // u = 32 s0 + 8 g + r: symbol s0 + g / 4 at lag 8 (g % 4) + r, and (r = 0, g % 4 = 0) the symbol
+            // before it at lag 32
+            const int sl = g >> 2;
+            if (sl < kCoSyms) {
+                const float sg = pr3[s0 + sl] ? 1.0f : -1.0f;
+#pragma unroll
+                for (int r = 0; r < 8; ++r) { acc_tp[r] += tp[r]; acc_ss[r] += sg * cm[r]; }
+            }
+            if ((g & 3) == 0 && sl > 0) {
+                acc_tp32 += tp[0];
+                acc_ss32 += (pr3[s0 + sl - 1] ? 1.0f : -1.0f) * cm[0];
+            }
+        }
+    }
+    __syncthreads();
+    float* __restrict__ red = &Bs[0][0];                               // [kCoThreads][kCoRed]
+#pragma unroll
+    for (int r = 0; r < 8; ++r) { red[kCoRed * tid + r] = acc_tp[r]; red[kCoRed * tid + 8 + r] = acc_ss[r]; }
+    red[kCoRed * tid + 16] = acc_tp32;
+    red[kCoRed * tid + 17] = acc_ss32;
+    red[kCoRed * tid + 18] = tall;
+    __syncthreads();
+    if (tid < kLpLags) {
+        const int m = tid;
+        float totp = 0.0f, ss = 0.0f, tm = 0.0f, dtab = 0.0f;
+        if (m < 32) {
+            for (int pair = 0; pair < 2; ++pair)
+                for (int g = (m >> 3) + kCoWork * pair; g < kCoWork - 1 + kCoWork * pair; g += 4) {
+                    totp += red[kCoRed * g + (m & 7)];
+                    ss += red[kCoRed * g + 8 + (m & 7)];
+                }
+        } else {
+            for (int pair = 0; pair < 2; ++pair)
+                for (int g = 4 + kCoWork * pair; g < kCoWork + kCoWork * pair; g += 4) {
+                    totp += red[kCoRed * g + 16];
+                    ss += red[kCoRed * g + 17];
+                }
+        }
+        for (int i = 0; i < kCoThreads; ++i) {
+            tm += red[kCoRed * i + 18];
+            const float d = dmax_s[i];
+            dtab = (d > dtab || d != d) ? d : dtab;
+        }
+        for (int v = m; v < 32; ++v) tm += tedge[v];                   // blocks m .. m + 5183 carry lag m's windows
+        for (int v = 0; v < m; ++v) tm += tedge[32 + v];
+        // eps(m), in double from the float sums
+        const double T = (double)tm * kLpTInflate, S = (double)totp, dt = (double)dtab + 1e-12;
+        const double kappa = dt + (kLpGammaRef + 3 * kLpU * (1 + kLpGammaRef)) * (1 + dt) + kLpCoarse;
+        const double E = 4 * kappa * T + kLpGammaFold * (S + 4 * kappa * T) + kLpAbs;
+        const double r = fabs((double)ss) / S;
+        const double eps = (E * (1 + r) / (S - E) + 4 * kLpU * (1 + r)) * (1 + 1e-6);
+        const float sy = ss / totp;
+        const bool ok = (S >= kLpTotpFloor) && (S > 4 * E) && (T < kLpTCeil) && (eps == eps) && (eps < 1.0) && (sy == sy) &&
+                        (fabsf(sy) <= 2.0f);
+        sy_s[m] = sy;
+        ep_s[m] = (float)(eps * (1 + 1e-6)) + 1e-9f;
+        bad_s[m] = ok ? 0 : 1;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        bool bad = false;
+        float lo = -3.0e38f;
+        for (int m = 0; m < kLpLags; ++m) {
+            bad |= bad_s[m] != 0;
+            // sync~ - eps and sync~ + eps rounded outwards (one ulp of a value below 4 is under 5e-7)
+            const float l = sy_s[m] - ep_s[m] - 1e-6f;
+            lo = l > lo ? l : lo;
+        }
+        unsigned long long mask = 0;
+        int n = 0;
+        for (int m = 0; m < kLpLags; ++m)
+            if (sy_s[m] + ep_s[m] + 1e-6f >= lo) { mask |= 1ull << m; ++n; }
+        if (bad || n > kLpCap || n == 0) {
+            fb_list[atomicAdd(&counts[1], 1)] = item;
+            mask = (1ull << kLpLags) - 1;
+            base_s = -1;
+        } else {
+            base_s = atomicAdd(&counts[0], n);
+            atomicAdd(&counts[2], 1);
+        }
+        mask_out[item] = mask;
+        mask_s = mask;
+    }
+    __syncthreads();
+    if (base_s >= 0 && tid < kLpLags) {
+        const unsigned long long mask = mask_s, bit = 1ull << tid;
+        if (mask & bit) exact_list[base_s + __builtin_popcountll(mask & (bit - 1))] = item * 64 + tid;
+        else sync_out[(size_t)item * kLpLags + tid] = -3.0e38f;        // never read (pick_lag_kernel's mask), and cannot win
+    }
+}
+
+// The reference's sums of ONE (candidate, lag) of the exact list: lane = symbol (162 of 192 lanes), the candidate's table
+// through the scalar cache, the samples through a chunked tile as in freq_scalar_kernel; amplitudes into the lag scan's
+// block.  Same operations per accumulator as demod_kernel => identical bits.
+constexpr int kLxThreads = 192;
+constexpr int kLxChunk = 16;
+constexpr int kLxPerThread = (kNSymD * kLxChunk + kLxThreads - 1) / kLxThreads;      // 14 samples staged per thread and chunk
+
+template <bool kFma>
+__global__ __launch_bounds__(kLxThreads)
+void lag_exact_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
+                      const FineState* __restrict__ items, const int* __restrict__ counts,
+                      const int* __restrict__ exact_list, const float* __restrict__ tabs, float4* __restrict__ pw_out) {
+    __shared__ float2 tile[kNSymD][kLxChunk + 1];
+    if ((int)blockIdx.x >= counts[0]) return;
+    const int code = exact_list[blockIdx.x], item = code >> 6, m = code & 63, tid = threadIdx.x;
+    const FineState st = items[item];
+    const float* __restrict__ xi = dI + (size_t)st.seg * kIqStride;
+    const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
+    const int lag = st.shift_coarse - 128 + 8 * m;
+    const float4* __restrict__ gt = reinterpret_cast<const float4*>(tabs) +
+                                    (size_t)__builtin_amdgcn_readfirstlane(st.pad) * 512;
+    const bool working = tid < kNSymD;
+    float2 nxt[kLxPerThread];
+    auto fetch = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < kLxPerThread; ++u) {
+            const int e = u * kLxThreads + tid, row = e / kLxChunk, col = e & (kLxChunk - 1);
+            const int k = lag + kSps * row + kLxChunk * c + col;
+            const bool ok = (e < kNSymD * kLxChunk) && (k > 0) && (k < np);     // wsprd.c:199; zero-fill == skip
+            nxt[u] = ok ? make_float2(xi[k], xq[k]) : make_float2(0.0f, 0.0f);
+        }
+    };
+    fetch(0);
+    ToneAcc<kFma> acc;
+    acc.clear();
+    for (int c = 0; c < kSps / kLxChunk; ++c) {
+        __syncthreads();                                             // the previous chunk has been consumed
+#pragma unroll
+        for (int u = 0; u < kLxPerThread; ++u) {
+            const int e = u * kLxThreads + tid;
+            if (e < kNSymD * kLxChunk) tile[e / kLxChunk][e & (kLxChunk - 1)] = nxt[u];
+        }
+        __syncthreads();
+        if (c + 1 < kSps / kLxChunk) fetch(c + 1);
+        if (working) {
+#pragma unroll 8
+            for (int jj = 0; jj < kLxChunk; ++jj) {
+                const int j = kLxChunk * c + jj;
+                acc.step(tile[tid][jj], gt[2 * j], gt[2 * j + 1]);
+            }
+        }
+    }
+    if (working) pw_out[((size_t)item * kLpLags + m) * kNSymD + tid] = acc.amplitudes();
+}
+
+// demod_metric_kernel (mode 0) over the rows the pruned scan filled: the exact list, then 33 lags per fallback candidate
+__global__ __launch_bounds__(64)
+void lag_metric_list_kernel(const float4* __restrict__ pw, const int* __restrict__ counts, const int* __restrict__ exact_list,
+                            const int* __restrict__ fb_list, float* __restrict__ sync_out,
+                            const unsigned char* __restrict__ pr3) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x, ne = counts[0], nf = counts[1];
+    int item, m;
+    if (idx < ne) {
+        const int code = exact_list[idx];
+        item = code >> 6; m = code & 63;
+    } else {
+        const int j = idx - ne;
+        if (j >= kLpLags * nf) return;
+        item = fb_list[j / kLpLags]; m = j % kLpLags;
+    }
+    const size_t row = (size_t)item * kLpLags + m;
+    const float4* __restrict__ P = pw + row * kNSymD;
+    sync_out[row] = sync_metric([&](int k) { return P[k]; }, pr3);
+}
+
+// mode 0 epilogue: first lag (in scan order) with the strictly largest metric; with a contender mask (lag pruning) only
+// the lags it names were summed, and the others are not read
 __global__ void pick_lag_kernel(FineState* __restrict__ items, int nitems,
-                                const float* __restrict__ sync_in, int nlag, int lagstep) {
+                                const float* __restrict__ sync_in, int nlag, int lagstep,
+                                const unsigned long long* __restrict__ mask) {
     const int it = blockIdx.x * blockDim.x + threadIdx.x;
     if (it >= nitems) return;
     FineState st = items[it];
     float best = -1e30f, fbest = 0.0f;
     int bshift = 0;
+    const unsigned long long lags = mask ? mask[it] : ~0ull;
     for (int m = 0; m < nlag; ++m) {
+        if (!((lags >> m) & 1)) continue;
         const float v = sync_in[(size_t)it * nlag + m];
         if (v > best) { best = v; bshift = st.shift_coarse - 128 + lagstep * m; fbest = st.freq_coarse; }
     }
@@ -1217,7 +1583,9 @@ struct TiledScan {
 
 // The amplitude kernels of a tiled scan at lag step STEP: drift-free candidates, then drifting ones
 template <int STEP, bool kFma>
-void launch_tile(const TiledScan& a) {
+void launch_tile(const TiledScan& a_in, bool shared_done) {
+    TiledScan a = a_in;
+    if (shared_done) a.n_shared = 0;                 // the lag pruning has served the drift-free candidates
     // WSPR_K4_LAG=tile: drift-free candidates' full lag scan on demod_tile_kernel<8, true> (one (symbol, lag) per lane,
     // samples in LDS) instead of the register-resident correlation
     static const bool lagsys_kernel = [] { const char* e = lab_env("WSPR_K4_LAG"); return !(e && e[0] == 't'); }();
@@ -1234,7 +1602,8 @@ void launch_tile(const TiledScan& a) {
     if (a.n_shared > 0 && full_scan && lagsys_kernel)
         for (int r = 0; r < rep_lag; ++r)
             hipLaunchKernelGGL(demod_lagsys_kernel<kFma>, dim3(kSysWaves * ((a.n_shared + 7) & ~7) + (a.n_shared + 63) / 64),
-                               dim3(64), 0, a.st, a.dI, a.dQ, a.samples, a.items, a.list_shared, a.n_shared, a.tabs, a.pw4);
+                               dim3(64), 0, a.st, a.dI, a.dQ, a.samples, a.items, a.list_shared, a.n_shared, a.tabs, a.pw4,
+                               (const int*)nullptr);
     else if (a.n_shared > 0)
         hipLaunchKernelGGL((demod_tile_kernel<STEP, true, kFma>), dim3(kNSymD / kTileSymsShared, a.n_shared),
                            threads(kTileSymsShared), tile_bytes(kTileSymsShared), a.st, a.dI, a.dQ, a.samples, a.items,
@@ -1251,21 +1620,50 @@ void launch_tile(const TiledScan& a) {
 }  // namespace
 
 // item_list_shared / item_list_own: indices into items[] of the candidates without / with drift
+size_t lag_prune_scratch_bytes(int nitems) {
+    return ((size_t)nitems * 8 + (size_t)nitems * (kLpCap + 1) * 4 + 15) & ~(size_t)15;
+}
+
 void launch_demod_tiled(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
                         const int* list_shared, int n_shared, const int* list_own, int n_own, int mode,
                         int nlag, int lagstep, float minsync1, const float* tabs, float* pw,
                         float* sync_out, unsigned char* sym_out, float* rms_out,
-                        const DeviceTables& t, hipStream_t st, int arith) {
+                        const DeviceTables& t, hipStream_t st, int arith, LagPrune* prune) {
+    if (prune) prune->mask = nullptr;
     if (nitems <= 0) return;
     const TiledScan a{dI, dQ, samples, items, list_shared, list_own, n_shared, n_own, mode, nlag, minsync1, tabs,
                       reinterpret_cast<float4*>(pw), st};
+    // WSPR_K4_LAG=full (or tile): every drift-free candidate through the whole scan, as before the lag pruning
+    static const bool whole_scan = [] { const char* e = lab_env("WSPR_K4_LAG"); return e && (e[0] == 'f' || e[0] == 't'); }();
+    const bool pruned = prune && !whole_scan && mode == 0 && lagstep == 8 && nlag == kLpLags && n_shared > 0;
     with_arith(arith, [&](auto fma) {
         constexpr bool kFma = decltype(fma)::value;
-        if (lagstep == 8) launch_tile<8, kFma>(a);
-        else if (lagstep == 16) launch_tile<16, kFma>(a);
-        else launch_tile<3, kFma>(a);
-        hipLaunchKernelGGL(demod_metric_kernel<kFma>, dim3((nitems * nlag + 63) / 64), dim3(64), 0, st, a.pw4, items, nitems,
-                           mode, nlag, minsync1, sync_out, sym_out, rms_out, t.sync);
+        if (pruned) {
+            // scratch: [contender masks: nitems x 8 bytes | exact list: kLpCap x n_shared | fallback list: n_shared]
+            unsigned long long* mask = reinterpret_cast<unsigned long long*>(prune->scratch);
+            int* exact_list = reinterpret_cast<int*>(mask + nitems);
+            prune->mask = mask;
+            int* fb_list = exact_list + (size_t)kLpCap * n_shared;
+            (void)hipMemsetAsync(mask, 0xff, (size_t)nitems * 8, st);            // drifting candidates: every lag
+            hipLaunchKernelGGL(lag_coarse_kernel, dim3(8 * ((n_shared + 7) >> 3)), dim3(kCoThreads), 0, st, dI, dQ, samples,
+                               items, list_shared, n_shared, tabs, t.sync, sync_out, prune->counts, exact_list, fb_list,
+                               mask);
+            hipLaunchKernelGGL(lag_exact_kernel<kFma>, dim3(kLpCap * n_shared), dim3(kLxThreads), 0, st, dI, dQ, samples, items,
+                               prune->counts, exact_list, tabs, a.pw4);
+            hipLaunchKernelGGL(demod_lagsys_kernel<kFma>, dim3(kSysWaves * ((n_shared + 7) & ~7) + (n_shared + 63) / 64),
+                               dim3(64), 0, st, dI, dQ, samples, items, fb_list, n_shared, tabs, a.pw4, prune->counts + 1);
+            hipLaunchKernelGGL(lag_metric_list_kernel, dim3(((kLpCap + kLpLags) * n_shared + 63) / 64), dim3(64), 0, st,
+                               a.pw4, prune->counts, exact_list, fb_list, sync_out, t.sync);
+        }
+        if (lagstep == 8) launch_tile<8, kFma>(a, pruned);
+        else if (lagstep == 16) launch_tile<16, kFma>(a, pruned);
+        else launch_tile<3, kFma>(a, pruned);
+        if (!pruned)
+            hipLaunchKernelGGL(demod_metric_kernel<kFma>, dim3((nitems * nlag + 63) / 64), dim3(64), 0, st, a.pw4, items, nitems,
+                               mode, nlag, minsync1, sync_out, sym_out, rms_out, t.sync);
+        else if (n_own > 0)
+            hipLaunchKernelGGL(demod_metric_kernel<kFma>, dim3((n_own * nlag + 63) / 64), dim3(64), 0, st, a.pw4, items, n_own,
+                               mode, nlag, minsync1, sync_out, sym_out, rms_out, t.sync, list_own);
     });
 }
 
@@ -1303,9 +1701,10 @@ double launch_calib_valu(float* out, int iters, hipStream_t st) {
 }
 #endif  // WSPR_LAB
 
-void launch_pick_lag(FineState* items, int nitems, const float* sync_in, int nlag, int lagstep, hipStream_t st) {
+void launch_pick_lag(FineState* items, int nitems, const float* sync_in, int nlag, int lagstep, hipStream_t st,
+                     const unsigned long long* mask) {
     if (nitems <= 0) return;
-    hipLaunchKernelGGL(pick_lag_kernel, dim3((nitems + 63) / 64), dim3(64), 0, st, items, nitems, sync_in, nlag, lagstep);
+    hipLaunchKernelGGL(pick_lag_kernel, dim3((nitems + 63) / 64), dim3(64), 0, st, items, nitems, sync_in, nlag, lagstep, mask);
 }
 void launch_pick_freq(FineState* items, int nitems, const float* sync_in, int nfreq, int ifmin,
                       float fstep, hipStream_t st, int arith) {

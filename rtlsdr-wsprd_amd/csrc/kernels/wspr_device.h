@@ -135,11 +135,22 @@ void launch_demod(const float* dI, const float* dQ, int samples, const FineState
 // item indices without / with drift.  mode 0: nlag lags shift_coarse-128 + lagstep*m;
 // mode 2: 43 lags shift-63+3*m (lagstep must be 3).  pw: nitems*nlag*162 float4 of scratch.
 void launch_phasor_tables(const FineState* items, int nitems, int mode, float* tabs, hipStream_t st, int arith);
+// Lag pruning of the full mode-0 scan (33 lags, step 8; k4_demod.hip): a cheap bounded pass names the lags that can still
+// win, exact sums are formed for those only.  The caller provides `scratch` (lag_prune_scratch_bytes(nitems) bytes) and
+// `counts`, three ints of device memory it has zeroed: [0] exact single-lag evaluations, [1] candidates that fell back
+// to the whole scan, [2] candidates pruned; launch_demod_tiled() sets `mask` (per item, bit m = lag m was summed; null
+// when it did not prune) for launch_pick_lag().
+struct LagPrune {
+    void* scratch;
+    int* counts;
+    const unsigned long long* mask;
+};
+size_t lag_prune_scratch_bytes(int nitems);
 void launch_demod_tiled(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
                         const int* list_shared, int n_shared, const int* list_own, int n_own, int mode,
                         int nlag, int lagstep, float minsync1, const float* tabs, float* pw,
                         float* sync_out, unsigned char* sym_out, float* rms_out,
-                        const DeviceTables& t, hipStream_t st, int arith);
+                        const DeviceTables& t, hipStream_t st, int arith, LagPrune* prune = nullptr);
 // mode 1 (5 frequencies) + first ladder rung; see k4_demod.hip.  tabs: n_shared*5 tables,
 // pw: n_shared*5*162 float4, scratch_sync: nitems*5 floats.
 void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int samples, FineState* items,
@@ -148,7 +159,8 @@ void launch_freq_scan_and_first_rung(const float* dI, const float* dQ, int sampl
                                      float* scratch_sync, float* sync_out, unsigned char* sym_out,
                                      float* rms_out, const DeviceTables& t, hipStream_t st,
                                      const float* pw_lag, int nlag_lag, int arith);
-void launch_pick_lag(FineState* items, int nitems, const float* sync_in, int nlag, int lagstep, hipStream_t st);
+void launch_pick_lag(FineState* items, int nitems, const float* sync_in, int nlag, int lagstep, hipStream_t st,
+                     const unsigned long long* mask = nullptr);
 void launch_pick_freq(FineState* items, int nitems, const float* sync_in, int nfreq, int ifmin,
                       float fstep, hipStream_t st, int arith);
 size_t subtract_scratch_floats(int njobs);
