@@ -1108,6 +1108,11 @@ void freq_metric_kernel(const float4* __restrict__ pw, FineState* __restrict__ i
 //   lag_metric_list_kernel   folds the (candidate, lag) rows those two wrote; pick_lag_kernel reads contenders only.
 // Lists and counts live in device memory and the follow-up grids are sized for the worst case (surplus workgroups
 // leave at once), so the wave needs no host wait in between.
+// Audit output (LagPrune::audit, null in the product and the lab library): what the proof of DESIGN.md section 4 talks
+// about lives in LDS and is gone after the launch, so with a non-null `audit` lane m of the final stage also stores
+// kLpAuditStride floats at audit[(item * 33 + m) * kLpAuditStride]: sync~(m), eps(m) as the contender rule reads it, totp~,
+// ss~, T~ (the float, before its inflation), delta_tab, and 1.0f / 0.0f = the lag was / was not flagged bad (a seventh
+// float, not a sign bit).  tools/lagprune_check.hip dumps them, tests/test_gpu_lag_coarse.py holds them against float64.
 constexpr int kLpLags = 33;
 constexpr int kLpCap = 4;                           // contenders a pruned candidate may have
 constexpr int kCoSyms = 27;                         // symbols per chunk of the coarse pass; 6 chunks
@@ -1132,13 +1137,14 @@ constexpr double kLpTInflate = 1 + 256 * kLpU;                         // T~ is 
 constexpr double kLpGammaFold = 648 * kLpU / (1 - 648 * kLpU) + 700 * kLpU / (1 - 700 * kLpU);   // (d) both folds
 constexpr double kLpAbs = 1e-15;                                       // underflow in squares, roots and products
 constexpr double kLpTotpFloor = 1e-9, kLpTCeil = 1e18;                 // outside: the standard model does not hold
+constexpr int kLpAuditStride = 7;                                      // floats per (item, lag) of the audit output
 
 __global__ __launch_bounds__(kCoThreads)
 void lag_coarse_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
                        const FineState* __restrict__ items, const int* __restrict__ item_list, int nitems,
                        const float* __restrict__ tabs, const unsigned char* __restrict__ pr3, float* __restrict__ sync_out,
                        int* __restrict__ counts, int* __restrict__ exact_list, int* __restrict__ fb_list,
-                       unsigned long long* __restrict__ mask_out) {
+                       unsigned long long* __restrict__ mask_out, float* __restrict__ audit) {
     __shared__ double2 e3d[4][8], e2d[4][32], ead[4][16], ebd[4][11];      // e^{i theta n}: n = j, 8 j, 256 j, 4096 j
     __shared__ float2 e3f[4][8], e2f[4][32], e1f[4][164];                  // in float: n = j, 8 j, 256 j
     __shared__ float Bs[8][kCoPitch];                                      // block sums: real parts of the 4 tones, imaginary parts
@@ -1333,8 +1339,13 @@ void lag_coarse_kernel(const float* __restrict__ dI, const float* __restrict__ d
         const bool ok = (S >= kLpTotpFloor) && (S > 4 * E) && (T < kLpTCeil) && (eps == eps) && (eps < 1.0) && (sy == sy) &&
                         (fabsf(sy) <= 2.0f);
         sy_s[m] = sy;
-        ep_s[m] = (float)(eps * (1 + 1e-6)) + 1e-9f;
+        const float ep = (float)(eps * (1 + 1e-6)) + 1e-9f;
+        ep_s[m] = ep;
         bad_s[m] = ok ? 0 : 1;
+        if (audit) {
+            float* __restrict__ a = audit + ((size_t)item * kLpLags + m) * kLpAuditStride;
+            a[0] = sy; a[1] = ep; a[2] = totp; a[3] = ss; a[4] = tm; a[5] = dtab; a[6] = ok ? 0.0f : 1.0f;
+        }
     }
     __syncthreads();
     if (tid == 0) {
@@ -1647,7 +1658,7 @@ void launch_demod_tiled(const float* dI, const float* dQ, int samples, const Fin
             (void)hipMemsetAsync(mask, 0xff, (size_t)nitems * 8, st);            // drifting candidates: every lag
             hipLaunchKernelGGL(lag_coarse_kernel, dim3(8 * ((n_shared + 7) >> 3)), dim3(kCoThreads), 0, st, dI, dQ, samples,
                                items, list_shared, n_shared, tabs, t.sync, sync_out, prune->counts, exact_list, fb_list,
-                               mask);
+                               mask, prune->audit);
             hipLaunchKernelGGL(lag_exact_kernel<kFma>, dim3(kLpCap * n_shared), dim3(kLxThreads), 0, st, dI, dQ, samples, items,
                                prune->counts, exact_list, tabs, a.pw4);
             hipLaunchKernelGGL(demod_lagsys_kernel<kFma>, dim3(kSysWaves * ((n_shared + 7) & ~7) + (n_shared + 63) / 64),

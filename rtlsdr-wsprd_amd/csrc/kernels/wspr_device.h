@@ -139,11 +139,14 @@ void launch_phasor_tables(const FineState* items, int nitems, int mode, float* t
 // win, exact sums are formed for those only.  The caller provides `scratch` (lag_prune_scratch_bytes(nitems) bytes) and
 // `counts`, three ints of device memory it has zeroed: [0] exact single-lag evaluations, [1] candidates that fell back
 // to the whole scan, [2] candidates pruned; launch_demod_tiled() sets `mask` (per item, bit m = lag m was summed; null
-// when it did not prune) for launch_pick_lag().
+// when it did not prune) for launch_pick_lag().  `audit` (null everywhere but in tools/lagprune_check.hip): nitems x 33 x 7
+// floats of device memory that receive the coarse pass' own numbers per (item, lag) -- sync~, eps, totp~, ss~, T~, delta_tab,
+// flagged bad (1.0f / 0.0f) -- for the drift-free candidates; see the pruning block of k4_demod.hip.
 struct LagPrune {
     void* scratch;
     int* counts;
     const unsigned long long* mask;
+    float* audit = nullptr;
 };
 size_t lag_prune_scratch_bytes(int nitems);
 void launch_demod_tiled(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,

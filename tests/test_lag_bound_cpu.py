@@ -89,12 +89,14 @@ def coarse_pass(I, Q, fc, sc, pr3, npts=NS):
     return sync, eps
 
 
-def oracle_sync(I, Q, fc, sc, m):
+def oracle_sync(I, Q, fc, sc, m, npts=NS, sync_demod=None):
+    """The reference's sync of the single lag m of a record of npts samples; sync_demod: another checker's entry of the
+    same signature (contract_lib's ctr_sync_demod) instead of the oracle's."""
     f, sh, dr, sy = C.c_float(fc), C.c_int(sc), C.c_float(0.0), C.c_float(0.0)
     sym = (C.c_ubyte * 162)()
     lag = sc - 128 + 8 * m
-    ol.lib().orc_sync_demod(ol.ptr(I), ol.ptr(Q), C.c_long(NS), sym, C.addressof(f), 0, 0, C.c_float(0.0),
-                            C.addressof(sh), lag, lag, 8, C.addressof(dr), 50, C.addressof(sy), 0)
+    (sync_demod or ol.lib().orc_sync_demod)(ol.ptr(I), ol.ptr(Q), C.c_long(npts), sym, C.addressof(f), 0, 0, C.c_float(0.0),
+                                            C.addressof(sh), lag, lag, 8, C.addressof(dr), 50, C.addressof(sy), 0)
     return np.float32(sy.value)
 
 
