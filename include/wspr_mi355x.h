@@ -371,7 +371,10 @@ void subtract_signal2(float *id, float *qd, long np, float f0, int shift, float 
  * then the lag pruning of the fine search's full lag scan (drift-free candidates), summed like the counts: [29] candidates
  * whose losing lags a bounded coarse pass ruled out, [30] the exact single-lag evaluations those candidates took
  * instead of 33 each, [31] candidates that fell back to the whole scan (too many contenders, or a quantity the bound
- * does not cover).
+ * does not cover);
+ * then the block-detection stage (wspr_set_block_detection(); all zero while it is off), summed like the counts: [32] the
+ * stage's wall time, milliseconds (K10, the Fano searches and their round trips), [33] soft-symbol vectors it sent to
+ * Fano, [34] and [35] the decodes it made at block size 2 and 3.
  * Returns the number of values written (<= capacity). */
 int wspr_last_timings(double *ms, int capacity);
 /* Worker threads of the library's host pools alive in this process (the threads that call into the library are
@@ -484,6 +487,56 @@ int wspr_set_arithmetic(int mode);
 int wspr_osd_batch_device(const unsigned char *symbols, int n, int depth, unsigned char *data, unsigned *dist,
                           unsigned *nhard, unsigned *order);
 int wspr_set_osd_depth(int depth);
+/* Noncoherent block detection, the demodulator behind what current WSJT-X wsprd offers as -B; the reference (v0.5.6)
+ * predates it, so there is no reference behaviour to match and the definition is this library's own, shaped after
+ * WSJT-X's noncoherent_sequence_detection() (rtlsdr-wsprd_amd/csrc/kernels/blockdemod.h; kernel K10).  For one hypothesis
+ * (freq, shift, drift) and a block size B of 1, 2 or 3 symbols:
+ *   the four tones' matched-filter sums of every symbol are those of sync_and_demodulate() mode 2 (wsprd.c:200-207, same
+ *   phasor tables, same order, same guard 0 < k < np), kept as complex numbers (is, qs) instead of magnitudes; for each
+ *   block of B consecutive symbols and each of its 2^B data-bit sequences (the first symbol's bit the most significant) the
+ *   B sums of the tones that sequence sends (tone = sync bit + 2 * data bit) are added coherently, each rotated back by
+ *   the phase its tone has gained over the symbols before it in the block (the table's recurrence one step past its last
+ *   entry):  xi += is*cm + qs*sm;  xq += qs*cm - is*sm;  (cm, sm) <- (cf*cm - sf*sm, sf*cm + cf*sm), from (1, 0);
+ *   p = sqrt(xi*xi + xq*xq).  A symbol's soft value is the largest p among the sequences in which its bit is 1 minus the
+ *   largest among those in which it is 0; normalisation and quantisation (symfac 50) are mode 2's.
+ * In the contracted arithmetic the statements fuse by the clang rule of wspr_set_arithmetic(), as written above.
+ * At B = 1 this is mode 2's vector bit for bit (on finite input), in both arithmetic modes.
+ *
+ * wspr_block_demod_batch(): host rows as wspr_decode_batch() takes them (nseg rows of `samples` floats, seg_stride
+ * apart) and n hypotheses; symbols[n][3][162] receives, per hypothesis, the vectors of B = 1, 2, 3 in transmission
+ * (interleaved) order, as wspr_fano_batch_device_wave() takes them.  It obeys wspr_set_arithmetic().  Returns 0; -1 with
+ * nothing written without a usable device, for samples > 45000 or < 0, n < 0, an item whose seg lies outside the batch or
+ * whose freq or drift is not finite; n == 0 does nothing.
+ *
+ * wspr_set_block_detection(): process-wide, 1 = off (the default), 2 or 3 = the largest block size of a stage that every
+ * decode call runs after the jitter ladder (read once per call, on entry, like wspr_set_osd_depth(); a WSPR_HASH_REVISIT
+ * call must run under the setting of the call it completes).  Returns the previous value; any other argument changes
+ * nothing and returns -2.  While it is on:
+ *   - the Fano budget split (wspr_set_fano_fast_budget) is off for the call -- results never depended on it;
+ *   - a candidate that was worth the jitter ladder (sync > minsync1) and decoded on none of its rungs is walked again:
+ *     for B = 2 .. maxblock, and for the rungs in the reference's ladder order (quickmode: jitter 0 only), the vector of
+ *     (B, rung) goes to the Fano search if the rung's mode-2 sync and the vector's own rms pass the gate of wsprd.c:758;
+ *     the first success in (B, rung) order wins;
+ *   - a success is a decode like any other -- spot, hash store, subtraction, de-duplication, loop exits -- reported with
+ *     the rung's jitter and Fano's cycles; the spot record has no room for B (the lab trace has);
+ *   - with wspr_set_osd_depth() on as well this stage runs first, and the ordered-statistics stage sees only what it left
+ *     undecoded (and uses the rung-0 vector of block size 1, as without this stage).
+ * What to expect: on a stable channel the larger blocks raise the quality of the soft symbols of a weak signal without
+ * any prior knowledge -- the Fano search validates a vector like any other, so no "heard before" gate is needed; drift or
+ * fading across a block lowers it.  On 24 synthetic single-signal segments at -30 dB (tests/synth.py, seeds 5000..5023,
+ * one pass, no subtraction) the plain decoder finds 6 and the stage's rule, stated on the CPU (tests/block_lib.py walk()),
+ * adds most of the rest with no false message, and none on noise (tools/block_rescue_seeds.py prints the table).  No gain
+ * is promised beyond that measured table (tools/block_sensitivity.py takes the curve).  A failing candidate costs up to
+ * 43 more demodulations and 86 more Fano searches.  The stage is OFF by default, and bench.py measures the default. */
+typedef struct {
+    int32_t seg;      /* row of the batch */
+    float   freq;     /* Hz relative to 1500 Hz, as sync_and_demodulate() takes *freq */
+    int32_t shift;    /* samples, jitter included */
+    float   drift;    /* Hz over the frame */
+} wspr_block_item;
+int wspr_block_demod_batch(const float *idat, const float *qdat, int nseg, int samples, size_t seg_stride,
+                           const wspr_block_item *items, int n, unsigned char *symbols);
+int wspr_set_block_detection(int maxblock);
 /* Library / device description, e.g. for bench logs. */
 const char *wspr_mi355x_version(void);
 int wspr_device_ready(void);        /* 1 if a HIP device and the kernels are usable */

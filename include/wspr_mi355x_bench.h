@@ -46,7 +46,9 @@ typedef struct wspr_cand_trace {
     unsigned char decdata[11];
     unsigned char stop;         /* the pass left the candidate loop here: 1 the decode did not re-encode (:786-788),
                                    2 its locator is "A000AA" (:791-793); 0 otherwise (was padding: the size is unchanged) */
-    unsigned char pad[2];
+    unsigned char block;        /* what decoded it: 0 undecoded, 1 the plain jitter ladder (or the ordered-statistics stage), 2 or 3
+                                   the block-detection stage at that block size (wspr_set_block_detection(); was padding) */
+    unsigned char pad[1];
 } wspr_cand_trace;
 typedef struct wspr_trace {
     int passes_run;

@@ -65,7 +65,8 @@ class cand_trace(C.Structure):               # include/wspr_mi355x_bench.h: wspr
                 ("freq", C.c_float), ("shift", C.c_int), ("drift", C.c_float), ("sync", C.c_float),
                 ("attempts", C.c_int), ("fano_calls", C.c_int), ("first_sync", C.c_float), ("first_rms", C.c_float),
                 ("decoded", C.c_int), ("subtracted", C.c_int), ("jitter", C.c_int), ("cycles", C.c_uint),
-                ("first_symbols", C.c_ubyte * NSYM), ("decdata", C.c_ubyte * 11), ("stop", C.c_ubyte), ("pad", C.c_ubyte * 2)]
+                ("first_symbols", C.c_ubyte * NSYM), ("decdata", C.c_ubyte * 11), ("stop", C.c_ubyte), ("block", C.c_ubyte),
+                ("pad", C.c_ubyte * 1)]
 
 
 class trace(C.Structure):                    # include/wspr_mi355x_bench.h: wspr_trace
@@ -126,6 +127,10 @@ def _bind(path):
     L.wspr_set_osd_depth.restype = C.c_int
     L.wspr_osd_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.wspr_osd_batch_device.restype = C.c_int
+    L.wspr_set_block_detection.argtypes = [C.c_int]
+    L.wspr_set_block_detection.restype = C.c_int
+    L.wspr_block_demod_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
+    L.wspr_block_demod_batch.restype = C.c_int
     L.wspr_synth_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int,
                                           C.c_void_p, C.c_void_p]
     L.wspr_synth_batch_device.restype = C.c_int
@@ -216,6 +221,37 @@ def osd_batch(symbols, depth, library=None):
     if rc != 0:
         raise RuntimeError("wspr_osd_batch_device failed (rc %d: depth outside 0..3, or no usable HIP device)" % rc)
     return data, dist, nhard, order
+
+
+# include/wspr_mi355x.h: wspr_block_item, one hypothesis of wspr_block_demod_batch()
+BLOCK_ITEM_DTYPE = np.dtype([("seg", "<i4"), ("freq", "<f4"), ("shift", "<i4"), ("drift", "<f4")])
+
+
+def set_block_detection(maxblock, library=None):
+    """wspr_set_block_detection() of include/wspr_mi355x.h: 1 switches the noncoherent block-detection stage off (the
+    default), 2 or 3 set the largest block size every later decode call tries.  Returns the previous value, or -2 (nothing
+    changed) for any other argument.  The product and the lab library each keep their own setting."""
+    return (library or lib()).wspr_set_block_detection(int(maxblock))
+
+
+def block_demod(I, Q, items, library=None):
+    """wspr_block_demod_batch(): host rows [nseg, samples] and n hypotheses (seg, freq, shift, drift) -- a numpy array of
+    BLOCK_ITEM_DTYPE or a list of such tuples.  Returns uint8 [n, 3, 162]: the soft-symbol vectors of block sizes 1, 2, 3 in
+    transmission order; raises if the library refuses the call."""
+    I = np.ascontiguousarray(I, dtype=np.float32)
+    Q = np.ascontiguousarray(Q, dtype=np.float32)
+    if I.ndim == 1:
+        I, Q = I[None, :], Q[None, :]
+    nseg, samples = I.shape
+    it = items if isinstance(items, np.ndarray) and items.dtype == BLOCK_ITEM_DTYPE else np.array(
+        [tuple(x) for x in items], BLOCK_ITEM_DTYPE)
+    it = np.ascontiguousarray(it)
+    n = int(it.size)
+    sym = np.zeros((n, 3, NSYM), np.uint8)
+    rc = (library or lib()).wspr_block_demod_batch(_ptr(I), _ptr(Q), nseg, samples, samples, _ptr(it), n, _ptr(sym))
+    if rc != 0:
+        raise RuntimeError("wspr_block_demod_batch failed (rc %d: bad arguments, or no usable HIP device)" % rc)
+    return sym
 
 
 def get_wspr_channel_symbols(message):
@@ -361,7 +397,8 @@ TIMING_NAMES = (
     "fano_left_to_device", "segments_redecoded", "candidates_consumed", "subtractions",
     "cpu_ms_call", "cpu_ms_pass_start", "cpu_ms_build_wave", "cpu_ms_refine", "cpu_ms_ladder", "cpu_ms_books",
     "cpu_ms_subtract", "cpu_ms_finish", "message_cache_lookups", "message_cache_hits",
-    "osd_ms", "osd_vectors", "osd_spots", "lag_pruned", "lag_exact_evals", "lag_fallbacks")
+    "osd_ms", "osd_vectors", "osd_spots", "lag_pruned", "lag_exact_evals", "lag_fallbacks",
+    "block_ms", "block_vectors", "block2_decodes", "block3_decodes")
 
 
 def last_timings():

@@ -91,6 +91,11 @@ int wspr_osd_batch_device(const unsigned char* symbols, int n, int depth, unsign
     } catch (const std::exception& e) { return fail("wspr_osd_batch_device", e); }
 }
 
+int wspr_set_block_detection(int maxblock) {
+    if (maxblock < 1 || maxblock > 3) return -2;
+    return wspr::block_setting().exchange(maxblock);
+}
+
 int wspr_host_pool_workers(void) { return wspr::pool_workers_alive().load(); }
 
 int wspr_last_timings(double* ms, int capacity) {

@@ -13,6 +13,8 @@
 #include <thread>
 #include <vector>
 
+#include <cmath>
+
 #include "wspr_capi_impl.h"
 
 using wspr::Context;
@@ -46,7 +48,8 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
     const int nslots = (nseg >= 128) ? Context::slot_cap() : 1;
     Context::note_slots_used(nslots);
     Context& c0 = Context::get();
-    const int dev = c0.device(), lane = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth();
+    const int dev = c0.device(), lane = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
+              maxblock = wspr::call_maxblock();
     struct Share { int lo, hi; };
     std::vector<Share> share(nslots);
     for (int g = 0; g < nslots; ++g) share[g] = {(int)((long)nseg * g / nslots), (int)((long)nseg * (g + 1) / nslots)};
@@ -61,6 +64,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
                 try {
                     wspr::ArithScope call_mode(arith);
                     wspr::OsdScope call_osd(osd_depth);
+                    wspr::BlockScope call_block(maxblock);
                     if (hipSetDevice(dev) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
                     Context::bind_lane(lane);
                     fn(g, Context::slot(g));
@@ -165,7 +169,7 @@ int decode_hashed(int nseg, int samples, const decoder_options& options, decoder
     const int nslots_now = (nseg >= 128) ? Context::slot_cap() : 1;
     if (revisit && !(t_hash && t_hash->valid && (int)t_hash->log.size() == nseg && t_hash->seg0 == seg_index0 &&
                      t_hash->samples == samples && t_hash->nslots == nslots_now && t_hash->arith == wspr::call_arith() &&
-                     t_hash->osd_depth == wspr::call_osd_depth()))
+                     t_hash->osd_depth == wspr::call_osd_depth() && t_hash->maxblock == wspr::call_maxblock()))
         throw std::runtime_error("WSPR_HASH_REVISIT without a matching, completed previous call on this thread");
     if (!revisit) {
         t_hash.reset(new wspr::HashBatch);
@@ -173,6 +177,7 @@ int decode_hashed(int nseg, int samples, const decoder_options& options, decoder
         t_hash->seg0 = seg_index0;
         t_hash->arith = wspr::call_arith();
         t_hash->osd_depth = wspr::call_osd_depth();
+        t_hash->maxblock = wspr::call_maxblock();
         t_hash->resize(nseg);
     }
     wspr::HashBatch& hb = *t_hash;
@@ -379,6 +384,20 @@ void sync_and_demodulate(float* id, float* qd, long np, unsigned char* symbols, 
         Context::get().demod_single(id, qd, np, symbols, freq, ifmin, ifmax, fstep, shift, lagmin, lagmax, lagstep,
                                     drift, sync, mode, symfac);
     } catch (const std::exception& e) { fail("sync_and_demodulate", e); }
+}
+
+int wspr_block_demod_batch(const float* idat, const float* qdat, int nseg, int samples, size_t seg_stride,
+                           const wspr_block_item* items, int n, unsigned char* symbols) {
+    static_assert(sizeof(wspr_block_item) == sizeof(wspr::BlockHyp), "wspr_block_item is the kernel's hypothesis");
+    if (n < 0 || nseg < 0 || samples < 0 || samples > wspr::kMaxSamples) return -1;
+    for (int i = 0; i < n; ++i)
+        if (items[i].seg < 0 || items[i].seg >= nseg || !std::isfinite(items[i].freq) || !std::isfinite(items[i].drift)) return -1;
+    if (n == 0) return 0;
+    LaneTurn lane_turn;
+    try {
+        return Context::get().block_demod_batch(idat, qdat, nseg, samples, seg_stride, reinterpret_cast<const wspr::BlockHyp*>(items), n,
+                                   symbols);
+    } catch (const std::exception& e) { return fail("wspr_block_demod_batch", e); }
 }
 
 void subtract_signal2(float* id, float* qd, long np, float f0, int shift, float drift,

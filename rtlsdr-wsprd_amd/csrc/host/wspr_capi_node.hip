@@ -77,7 +77,9 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
     NodeShareGuard share(ndevices);
     wspr::ArithScope call_mode;
     wspr::OsdScope call_osd;
-    const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth();
+    wspr::BlockScope call_block;
+    const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
+              maxblock = wspr::call_maxblock();
     int home = 0;
     (void)hipGetDevice(&home);
     std::vector<int> rcs(ndevices, 0);
@@ -89,6 +91,7 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
         th.emplace_back([=, &rcs] {
             wspr::ArithScope worker_mode(arith);
             wspr::OsdScope worker_osd(osd_depth);
+            wspr::BlockScope worker_block(maxblock);
             if (hipSetDevice(k % count) != hipSuccess) {
                 rcs[k] = -1;
                 for (int s = lo; s < hi; ++s) n_results[s] = 0;
@@ -143,7 +146,9 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
     NodeShareGuard share(ndevices);
     wspr::ArithScope call_mode;
     wspr::OsdScope call_osd;
-    const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth();
+    wspr::BlockScope call_block;
+    const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
+              maxblock = wspr::call_maxblock();
     std::vector<int> rcs(ndevices, 0);
     std::vector<std::thread> th;
     for (int k = 0; k < ndevices; ++k) {
@@ -153,6 +158,7 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
         th.emplace_back([=, &rcs] {
             wspr::ArithScope worker_mode(arith);
             wspr::OsdScope worker_osd(osd_depth);
+            wspr::BlockScope worker_block(maxblock);
             const int dev = k % count;
             if (hipSetDevice(dev) != hipSuccess) { rcs[k] = -1; return; }
             Context::bind_lane(lane0 + k / count);

@@ -197,10 +197,10 @@ size_t Context::release_buffers() {
                               &c.symbuf, &c.rmsbuf, &c.jobs, &c.subscratch, &c.nvalid, &c.decscratch, &c.tabs, &c.pw, &c.pwfreq, &c.lagprune,
                               &c.lists, &c.scrsync, &c.psavg, &c.densein, &c.fz_sym, &c.fz_off, &c.fz_ret, &c.fz_cyc, &c.fz_met, &c.fz_max,
                               &c.fz_dat, &c.fz_steps, &c.fz_pool, &c.streamraw, &c.streamstate, &c.synthtx, &c.synthoff, &c.synthfirst,
-                              &c.synthckpt, &c.synthrows})
+                              &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out})
                 freed += b->release();
             for (PinBuf* b : {&c.h_npk, &c.h_cand, &c.h_items, &c.h_sync, &c.h_sym, &c.h_rms, &c.h_jobs, &c.h_jobs2, &c.h_seglist,
-                              &c.h_misc, &c.h_lists, &c.h_fz, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
+                              &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
                 b->release();
             c.stage_samples[0] = c.stage_samples[1] = 0;
             free(c.hash_arena);
@@ -495,6 +495,38 @@ void Context::demod_single(float* id, float* qd, long np, unsigned char* symbols
     HIP_OK(hipMemcpyAsync(&f, d_items, sizeof f, hipMemcpyDeviceToHost, c.stream));
     HIP_OK(hipStreamSynchronize(c.stream));
     *sync = f.sync; *shift = f.shift; *freq = f.freq;
+}
+
+// K10 over n hypotheses on the working rows (the decode loop's block stage): results on the host, symbols n*3*162 (block
+// sizes 1, 2, 3), rms n*3 and sync n (either may be null).  d_symbols (may be null): where the vectors stay in HBM.
+int Context::block_resident(const BlockHyp* hyps, int n, int samples, unsigned char* symbols, float* rms_out,
+                            float* sync_out, const unsigned char** d_symbols) {
+    Impl& c = *d;
+    if (d_symbols) *d_symbols = nullptr;
+    if (n <= 0) return 0;
+    BlockHyp* dh = static_cast<BlockHyp*>(c.blk_hyp.need((size_t)n * sizeof(BlockHyp)));
+    // one result block [sync | rms | symbols]: one copy down
+    const size_t o_rms = (size_t)n * 4, o_sym = o_rms + (size_t)n * 12, blk = o_sym + (size_t)n * 3 * kNSymD;
+    char* dout = static_cast<char*>(c.blk_out.need(blk));
+    char* hout = static_cast<char*>(c.h_blk.need(blk));
+    upload(dh, hyps, (size_t)n * sizeof(BlockHyp), c.stream);
+    launch_block_demod(c.iqI.as<float>(), c.iqQ.as<float>(), samples, dh, n, reinterpret_cast<unsigned char*>(dout + o_sym),
+                       reinterpret_cast<float*>(dout + o_rms), reinterpret_cast<float*>(dout), c.tab, c.stream, call_arith());
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(hout, dout, symbols ? blk : o_sym, hipMemcpyDeviceToHost, c.stream));
+    sync();
+    if (sync_out) memcpy(sync_out, hout, (size_t)n * 4);
+    if (rms_out) memcpy(rms_out, hout + o_rms, (size_t)n * 12);
+    if (symbols) memcpy(symbols, hout + o_sym, (size_t)n * 3 * kNSymD);
+    if (d_symbols) *d_symbols = reinterpret_cast<const unsigned char*>(dout + o_sym);
+    return 0;
+}
+
+// K10 over host rows (wspr_block_demod_batch): the caller has validated the items against nseg
+int Context::block_demod_batch(const float* I, const float* Q, int nseg, int samples, size_t stride, const BlockHyp* hyps,
+                               int n, unsigned char* symbols) {
+    load_host(I, Q, nseg, samples, stride);
+    return block_resident(hyps, n, samples, symbols, nullptr, nullptr);
 }
 
 void Context::subtract_single(float* id, float* qd, long np, float f0, int shift, float drift,

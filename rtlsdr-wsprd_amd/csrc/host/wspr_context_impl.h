@@ -250,6 +250,8 @@ struct Context::Impl {
     PinBuf h_fz;                     // K6w's results on their way to the host (a copy into pageable memory would make
                                      // the runtime wait for the search itself, on a CPU)
     PinBuf h_osd;                    // K9's results on their way to the host
+    DevBuf blk_hyp, blk_out;         // K10: the hypotheses, and [sync | rms | symbols] of each
+    PinBuf h_blk;                    // ... on their way to the host
     PinBuf h_stage[2];
     PinBuf h_streamraw, h_streamstate, h_streamout;   // many receivers' callbacks at once (decimate_stream_many)
     hipEvent_t ev_stage[2] = {nullptr, nullptr};

@@ -46,6 +46,7 @@ struct HashBatch {
     int nslots = 0, samples = 0;
     int arith = 0;                                  // wspr_set_arithmetic() mode of the call (a revisit must match it)
     int osd_depth = -1;                             // wspr_set_osd_depth() of the call (a revisit must match it too)
+    int maxblock = 1;                               // wspr_set_block_detection() of the call (likewise)
 
     HashBatch();
     void load_file();                               // hashtable.txt of the working directory (wsprd.c:481-494)

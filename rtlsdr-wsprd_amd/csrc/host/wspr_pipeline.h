@@ -58,6 +58,20 @@ struct OsdScope {
     OsdScope& operator=(const OsdScope&) = delete;
 };
 
+// wspr_set_block_detection(): the process-wide largest block size of the block-detection stage (1 off, 2, 3).  Read ONCE
+// per call, on entry, and handed to the threads a call starts for itself, exactly as the two settings above.
+std::atomic<int>& block_setting();
+int& call_block_slot();                                   // thread-local: the current call's value, 0 outside a call
+inline int call_maxblock() { const int m = call_block_slot(); return m == 0 ? block_setting().load() : m; }
+struct BlockScope {
+    bool owner;
+    BlockScope() : owner(call_block_slot() == 0) { if (owner) call_block_slot() = block_setting().load(); }
+    explicit BlockScope(int maxblock) : owner(call_block_slot() == 0) { if (owner) call_block_slot() = maxblock; }
+    ~BlockScope() { if (owner) call_block_slot() = 0; }
+    BlockScope(const BlockScope&) = delete;
+    BlockScope& operator=(const BlockScope&) = delete;
+};
+
 // The values of wspr_last_timings(), in the order include/wspr_mi355x.h documents (that order is ABI; the Python
 // wrapper's TIMING_NAMES repeats it).  A new value goes at the end, here and in both of those.
 enum TimingSlot : int {
@@ -69,6 +83,7 @@ enum TimingSlot : int {
     kTmMessageCacheLookups, kTmMessageCacheHits,
     kTmOsdMs, kTmOsdVectors, kTmOsdSpots,
     kTmLagPruned, kTmLagExactEvals, kTmLagFallbacks,
+    kTmBlockMs, kTmBlockVectors, kTmBlock2Decodes, kTmBlock3Decodes,
     kTimingSlots
 };
 // A batch runs on several pipelines at once and each keeps its own values; wspr_last_timings() folds them.  The stage
@@ -76,7 +91,7 @@ enum TimingSlot : int {
 // from it on is SUMMED -- the counts, and the CPU times kTmCpuMs* as well (CPU time spent on different threads adds
 // up; the public header says "summed over the slots").
 constexpr int kTimingFirstSummed = kTmFanoCalls;
-static_assert(kTimingSlots == 32 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
+static_assert(kTimingSlots == 36 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
 
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt
@@ -178,6 +193,12 @@ public:
                   unsigned* order);
     int osd_resident(const unsigned char* d_symbols, const int* h_offsets, int n, int depth, unsigned char* data,
                      unsigned* dist, unsigned* nhard, unsigned* order);
+    // K10 (k10_blockdemod.hip; the definition in kernels/blockdemod.h): the vectors of block sizes 1, 2, 3 of n hypotheses,
+    // on the working rows (results on the host; rms n*3, sync n and d_symbols may be null) and over host rows
+    int block_resident(const BlockHyp* hyps, int n, int samples, unsigned char* symbols, float* rms_out, float* sync_out,
+                       const unsigned char** d_symbols = nullptr);
+    int block_demod_batch(const float* I, const float* Q, int nseg, int samples, size_t stride, const BlockHyp* hyps, int n,
+                          unsigned char* symbols);
     int bench_decimate(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int iters, double* ms);
     int decimate_device(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int normalise,
                         int* h_nout, DecimState* d_states = nullptr);

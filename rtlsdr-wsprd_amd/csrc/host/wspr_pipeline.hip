@@ -215,6 +215,15 @@ int& call_osd_slot() {
     return m;
 }
 
+std::atomic<int>& block_setting() {
+    static std::atomic<int> v{1};
+    return v;
+}
+int& call_block_slot() {
+    thread_local int m = 0;
+    return m;
+}
+
 std::atomic<unsigned>& fano_fast_budget() {
     static std::atomic<unsigned> v{[] { const char* e = getenv("WSPR_FANO_FAST"); return e ? (unsigned)atoi(e) : 10000u; }()};
     return v;
@@ -251,8 +260,9 @@ int Context::decode_resident(int nseg, int samples, const decoder_options& opt, 
     // (a shared hash memory keeps the host's full budget too: a provisional failure would log look-ups of a decode
     // that is thrown away)
     // (and so does the ordered-statistics stage: it takes the candidates whose every Fano attempt FAILED, which a
-    // provisional failure is not)
-    const unsigned fast = (reload && nseg >= 256 && !dev_fano && !trace && !hb && call_osd_depth() < 0) ? std::min(fast_cfg, 10000u) : 0u;
+    // provisional failure is not; the block-detection stage likewise)
+    const unsigned fast = (reload && nseg >= 256 && !dev_fano && !trace && !hb && call_osd_depth() < 0 && call_maxblock() <= 1)
+                              ? std::min(fast_cfg, 10000u) : 0u;
     if (trace) memset(trace, 0, (size_t)nseg * sizeof(wspr_trace));
     d->dev_fano = dev_fano;
     std::vector<int> all(nseg);
@@ -323,6 +333,11 @@ struct Context::DecodeRun {
     std::vector<char> gate0, by_osd;
     std::atomic<long> n_osd_spots{0};         // candidates the gate let through (bookkeeping runs on the pool's threads)
     const unsigned char* d_sym0 = nullptr;    // the wave's rung-0 soft symbols in HBM
+    // wspr_set_block_detection() of this call (1: off), and per item of the current wave the block size that decoded it
+    // (0: not this stage)
+    const int maxblock = call_maxblock();
+    std::vector<unsigned char> by_block;
+    std::atomic<long> n_block_decodes[2] = {{0}, {0}};   // consumed decodes by block size 2 and 3
 
     // one Fano attempt on a soft-symbol vector in transmission order (wsprd.c:759-761)
     int fano_attempt(const unsigned char* tx_sym, unsigned* cycles, unsigned char* data11) const {
@@ -403,6 +418,7 @@ struct Context::DecodeRun {
     std::vector<WaveItem> build_wave(const std::vector<int>& active);
     void refine_and_first_rung(std::vector<WaveItem>& wave);
     void remaining_rungs(std::vector<WaveItem>& wave);
+    void block_rescue(std::vector<WaveItem>& wave);
     void osd_rescue(std::vector<WaveItem>& wave);
     std::vector<SubJob> keep_books(std::vector<WaveItem>& wave);
     void subtract(const std::vector<SubJob>& jobs);
@@ -802,6 +818,95 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
     }
 }
 
+// Noncoherent block detection (wspr_set_block_detection() >= 2; the definition in kernels/blockdemod.h): every candidate
+// of the wave that was worth the jitter ladder and decoded on none of its rungs is walked again.  For B = 2 .. maxblock
+// and the rungs in the ladder's order (quick mode: jitter 0 only) the vector of (B, rung) goes to Fano if it passes the
+// gate of wsprd.c:758 -- the rung's mode-2 sync against minsync2, the vector's own rms against minrms; the first success
+// in (B, rung) order wins.  K10 forms all the vectors of a chunk of candidates at once, every gated one is searched (host
+// pool or K6w, as the ladder) and the pick is made afterwards.  A success is a decode like any other.
+void Context::DecodeRun::block_rescue(std::vector<WaveItem>& wave) {
+    const int nw = (int)wave.size();
+    by_block.assign(nw, 0);
+    std::vector<int> todo;
+    for (int i = 0; i < nw; ++i)
+        if (wave[i].worth && !wave[i].decoded) todo.push_back(i);
+    if (todo.empty()) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int nr = opt.quickmode ? 1 : kMaxLags, nb = maxblock - 1;
+    constexpr int kChunk = 256;                                // candidates per K10 launch: 43 x 3 vectors each, 5.6 MB down
+    std::vector<BlockHyp> hyps;
+    std::vector<unsigned char> sym;
+    std::vector<float> rms, sy;
+    for (int lo = 0; lo < (int)todo.size(); lo += kChunk) {
+        const int na = std::min(kChunk, (int)todo.size() - lo), nh = na * nr;
+        hyps.resize(nh);
+        for (int a = 0; a < na; ++a) {
+            const FineState& f = wave[todo[lo + a]].fine;
+            for (int r = 0; r < nr; ++r) hyps[(size_t)a * nr + r] = BlockHyp{f.seg, f.freq, f.shift + c.jitter_ladder[r], f.drift};
+        }
+        rms.resize((size_t)nh * 3);
+        sy.resize(nh);
+        if (!c.dev_fano) sym.resize((size_t)nh * 3 * kNSymD);
+        const unsigned char* d_vec = nullptr;
+        ctx.block_resident(hyps.data(), nh, samples, c.dev_fano ? nullptr : sym.data(), rms.data(), sy.data(), &d_vec);
+        // attempts in the walk's order per candidate: B = 2 .. maxblock, then rung; `off` = the vector's index among the 3 nh
+        std::vector<int> off, who;
+        for (int a = 0; a < na; ++a)
+            for (int b = 0; b < nb; ++b)
+                for (int r = 0; r < nr; ++r) {
+                    const size_t h = (size_t)a * nr + r;
+                    if (sy[h] > minsync2 && rms[h * 3 + b + 1] > minrms) { off.push_back((int)(h * 3 + b + 1)); who.push_back((a * nb + b) * nr + r); }
+                }
+        const int nv = (int)off.size(), per = nb * nr;
+        std::vector<int> ret(nv, -1);
+        std::vector<unsigned> cyc(nv, 0);
+        std::vector<unsigned char> dat((size_t)nv * 11, 0);
+        if (c.dev_fano) {
+            std::vector<unsigned char> d10((size_t)nv * 10);
+            ctx.fano_resident(d_vec, off.data(), nv, 10000u, ret.data(), cyc.data(), d10.data());
+            for (int k = 0; k < nv; ++k) memcpy(dat.data() + (size_t)k * 11, d10.data() + (size_t)k * 10, 10);
+        } else {
+            // attempt-major order and one task per grab, as the ladder: early attempts finish first and cancel the later
+            // ones of the same candidate
+            std::vector<std::atomic<int>> first(na);
+            for (auto& f : first) f.store(per);
+            std::vector<int> order(nv);
+            for (int k = 0; k < nv; ++k) order[k] = k;
+            std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return who[x] % per < who[y] % per; });
+            Pool& fpool = (nv >= 256) ? *c.bigpool : *c.pool;
+            fpool.run(nv, [&](int task) {
+                const int k = order[task], a = who[k] / per, q = who[k] % per;
+                if (q > first[a].load()) return;                // an earlier attempt already decoded
+                ret[k] = fano_attempt(sym.data() + (size_t)off[k] * kNSymD, &cyc[k], dat.data() + (size_t)k * 11);
+                if (ret[k] == 0) {
+                    int cur = first[a].load();
+                    while (q < cur && !first[a].compare_exchange_weak(cur, q)) {}
+                }
+            }, 1);
+        }
+        std::vector<int> first(na, per), at(na, -1);
+        for (int k = 0; k < nv; ++k) {
+            const int a = who[k] / per, q = who[k] % per;
+            if (ret[k] == 0 && q < first[a]) { first[a] = q; at[a] = k; }
+        }
+        for (int k = 0; k < nv; ++k) {                         // what the serial walk would have run
+            const int a = who[k] / per, q = who[k] % per;
+            if (q > first[a]) continue;
+            c.n_fano++; c.n_cycles += cyc[k]; if (ret[k]) c.n_timeout++;
+            c.t_ms[kTmBlockVectors] += 1.0;
+        }
+        for (int a = 0; a < na; ++a) {
+            if (at[a] < 0) continue;
+            const int i = todo[lo + a], b = first[a] / nr, r = first[a] % nr;
+            WaveItem& w = wave[i];
+            by_block[i] = (unsigned char)(b + 2);
+            w.decoded = true; w.jitter = c.jitter_ladder[r]; w.cycles = cyc[at[a]];
+            memcpy(w.decdata, dat.data() + (size_t)at[a] * 11, 11);
+        }
+    }
+    c.t_ms[kTmBlockMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
 // Ordered-statistics rescue (wspr_set_osd_depth() >= 0): every candidate of the wave that was worth a ladder, whose
 // every Fano attempt failed and whose rung-0 vector passed the sync/rms gate goes through K9, straight from the rung-0
 // symbols in HBM (the ladder's upload only rewrote the head of that block, the items).  The result is provisional: it
@@ -878,10 +983,12 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
             if (t.attempts > 0) { tc->first_sync = t.sync0; tc->first_rms = t.rms0; memcpy(tc->first_symbols, t.sym0, kNSymD); }
             if (w.worth && w.decoded) {
                 tc->decoded = 1; tc->jitter = w.jitter; tc->cycles = w.cycles;
+                tc->block = (maxblock > 1 && by_block[i]) ? by_block[i] : 1;
                 memcpy(tc->decdata, w.decdata, 11);
             }
         }
         if (!(w.worth && w.decoded)) continue;
+        if (maxblock > 1 && by_block[i]) n_block_decodes[by_block[i] - 2]++;
 
         signed char message[12] = {0};
         for (int k = 0; k < 11; ++k) message[k] = (signed char)w.decdata[k];
@@ -1036,6 +1143,7 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
             if (wave.empty()) break;
             { CpuSpan sp(&d->t_ms[kTmCpuMsRefine]); run.refine_and_first_rung(wave); }
             { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.remaining_rungs(wave); }
+            if (run.maxblock > 1) { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.block_rescue(wave); }
             if (run.osd_depth >= 0) { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.osd_rescue(wave); }
             std::vector<SubJob> jobs;
             { CpuSpan sp(&d->t_ms[kTmCpuMsBooks]); jobs = run.keep_books(wave); }
@@ -1044,6 +1152,8 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
     }
     { CpuSpan sp(&d->t_ms[kTmCpuMsFinish]); run.finish(active0, n_results); }
     d->t_ms[kTmOsdSpots] += (double)run.n_osd_spots.load();
+    d->t_ms[kTmBlock2Decodes] += (double)run.n_block_decodes[0].load();
+    d->t_ms[kTmBlock3Decodes] += (double)run.n_block_decodes[1].load();
     guard.armed = false;
     return 0;
 }

@@ -188,6 +188,18 @@ void launch_fano_wave(const unsigned char* symbols, const int* offsets, int n, c
 // (osd::pack_generator_row).  Outputs per vector: data[11], dist, nhard, order.
 void launch_osd(const unsigned char* symbols, const int* offsets, int n, int depth, const uint32_t* gen,
                 unsigned char* data, unsigned* dist, unsigned* nhard, unsigned* order, hipStream_t st);
+// K10, noncoherent block detection (k10_blockdemod.hip; the definition in blockdemod.h).  BlockHyp is wspr_block_item of the
+// public header: one hypothesis, `shift` with the rung's jitter already added.  Per hypothesis h: sym_out[h][3][162] (block
+// sizes 1, 2, 3, transmission order), rms_out[h][3] and sync_out[h], the mode-2 sync of the hypothesis.
+struct BlockHyp {
+    int32_t seg;
+    float freq;
+    int32_t shift;
+    float drift;
+};
+void launch_block_demod(const float* dI, const float* dQ, int samples, const BlockHyp* hyps, int nhyp,
+                        unsigned char* sym_out, float* rms_out, float* sync_out, const DeviceTables& t, hipStream_t st,
+                        int arith);
 // K8, the signal synthesiser (k8_synth.hip; arithmetic in synth_math.h).  SynthTx is wspr_synth_tx of the public header.
 struct SynthTx {
     int32_t seg;
