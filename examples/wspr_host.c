@@ -20,6 +20,9 @@
  *                        (wspr_session_feed_many()), and at the even minute all completed buffers are decoded together
  *                        (wspr_session_decode_many()); lines carry "[k] " in front.
  *   decoder options      -f dial Hz, -c call, -l locator, -H, -Q, -S as rtlsdr_wsprd.c:862-970.
+ *   -W                   (before -r or -t) switches the Doppler-spread stage on (wspr_set_spread_estimate()) and appends
+ *                        " w50 <Hz>" to every spot line ("w50 -" where the figure is not valid).  Without it the output is
+ *                        what it always was.  The receiver sessions (-i) keep no such records: -W changes nothing there.
  *
  * Build: make -C examples      (gcc, links ../rtlsdr-wsprd_amd/libwspr_mi355x.so with an rpath)
  */
@@ -41,8 +44,18 @@ static const char kHeader[] = "        SNR      DT        Freq Dr    Call    Loc
 
 static void usage(const char *argv0) {
     fprintf(stderr,
-            "use: %s [-f dial_hz] [-c call] [-l locator] [-H] [-Q] [-S] (-r FILE [FILE ...] | -t | -i RAWFILE|- [-i RAWFILE ...] [-T utc_seconds])\n",
+            "use: %s [-f dial_hz] [-c call] [-l locator] [-H] [-Q] [-S] [-W] (-r FILE [FILE ...] | -t | -i RAWFILE|- [-i RAWFILE ...] [-T utc_seconds])\n",
             argv0);
+}
+
+static int g_spread = 0;                   /* -W */
+
+/* " w50 <Hz>" of record r, or nothing without -W */
+static void spread_suffix(const wspr_spread *r, char *out, size_t cap) {
+    out[0] = '\0';
+    if (!g_spread) return;
+    if (r && r->valid) snprintf(out, cap, " w50 %.3f", r->w50);
+    else snprintf(out, cap, " w50 -");
 }
 
 static int has_suffix(const char *name, const char *suffix) {
@@ -79,17 +92,25 @@ static int playback(int nfiles, char **files, struct decoder_options opt) {
         if (nfiles == 1 && nread[0] <= 0) nspots[0] = 0;
         if (r < 0) { fprintf(stderr, "decode failed (%d): no usable MI355X\n", r); rc = 3; }
     }
+    /* the records follow the layout of `spots`: entry k * MAX_SPOTS + s of the batch call, entry s of the single call */
+    wspr_spread *spread = NULL;
+    if (g_spread && rc == 0) {
+        spread = calloc((size_t)nfiles * MAX_SPOTS, sizeof *spread);
+        if (spread && wspr_last_spreads(spread, nfiles * MAX_SPOTS) < 0) { free(spread); spread = NULL; }
+    }
     for (int k = 0; k < nfiles && rc == 0; ++k) {
         if (nfiles > 1) printf("%s\n", files[k]);
         printf("Number of samples: %d\n", nread[k]);
         if (nread[k] <= 0) continue;
         printf("%s\n", kHeader);
         for (int s = 0; s < nspots[k]; ++s) {
-            char line[128];
+            char line[128], tail[32];
             wspr_format_spot(&spots[(size_t)k * MAX_SPOTS + s], line, sizeof line);
-            printf("%s\n", line);
+            spread_suffix(spread ? &spread[(size_t)k * MAX_SPOTS + s] : NULL, tail, sizeof tail);
+            printf("%s%s\n", line, tail);
         }
     }
+    free(spread);
     free(I); free(Q); free(spots); free(nspots); free(nread);
     return rc;
 }
@@ -131,9 +152,14 @@ static int self_test(struct decoder_options opt) {
     const int r = wspr_decode(I, Q, SLOT_SAMPLES, opt, spots, &n);
     if (r < 0) { fprintf(stderr, "decode failed (%d): no usable MI355X\n", r); return 3; }
     printf("%s\n", kHeader);
-    for (int s = 0; s < n; ++s)
-        printf("Spot(%i) %6.2f %6.2f %10.6f %2d %7s %6s %2s\n", s, spots[s].snr, spots[s].dt, spots[s].freq,
-               (int)spots[s].drift, spots[s].call, spots[s].loc, spots[s].pwr);
+    wspr_spread spread[MAX_SPOTS];
+    const int have_spread = g_spread && wspr_last_spreads(spread, MAX_SPOTS) >= n;
+    for (int s = 0; s < n; ++s) {
+        char tail[32];
+        spread_suffix(have_spread ? &spread[s] : NULL, tail, sizeof tail);
+        printf("Spot(%i) %6.2f %6.2f %10.6f %2d %7s %6s %2s%s\n", s, spots[s].snr, spots[s].dt, spots[s].freq,
+               (int)spots[s].drift, spots[s].call, spots[s].loc, spots[s].pwr, tail);
+    }
     const int ok = n > 0 && !strcmp(spots[0].call, "K1JT") && !strcmp(spots[0].loc, "FN20") && !strcmp(spots[0].pwr, "20");
     printf("%s\n", ok ? "Self-test SUCCESS!" : "Self-test FAILED!");
     return ok ? 0 : 1;
@@ -249,6 +275,7 @@ int main(int argc, char **argv) {
             case 'H': opt.usehashtable = 1; break;
             case 'Q': opt.quickmode = 1; break;
             case 'S': opt.subtraction = 0; opt.npasses = 1; break;
+            case 'W': g_spread = 1; break;
             case 't': mode = SELFTEST; break;
             case 'T': t0 = strtol(argv[++a], NULL, 10); break;
             case 'i':                                                           /* one receiver per -i */
@@ -262,6 +289,7 @@ int main(int argc, char **argv) {
     }
     if (mode == NONE || (mode == PLAYBACK && first_file >= argc)) { usage(argv[0]); return 2; }
     if (!wspr_device_ready()) { fprintf(stderr, "%s: no usable MI355X (there is no CPU fallback)\n", wspr_mi355x_version()); return 3; }
+    if (g_spread) wspr_set_spread_estimate(1);
     switch (mode) {
         case PLAYBACK: return playback(argc - first_file, argv + first_file, opt);
         case SELFTEST: return self_test(opt);

@@ -374,7 +374,10 @@ void subtract_signal2(float *id, float *qd, long np, float f0, int shift, float 
  * does not cover);
  * then the block-detection stage (wspr_set_block_detection(); all zero while it is off), summed like the counts: [32] the
  * stage's wall time, milliseconds (K10, the Fano searches and their round trips), [33] soft-symbol vectors it sent to
- * Fano, [34] and [35] the decodes it made at block size 2 and 3.
+ * Fano, [34] and [35] the decodes it made at block size 2 and 3;
+ * then the Doppler-spread stage (wspr_set_spread_estimate(); both zero while it is off), summed like the counts: [36] the
+ * stage's device time, milliseconds (K11 with its transfers, taken without a host wait like the subtraction's), [37] the
+ * spread jobs it ran (one per spot the call's decode loops added).
  * Returns the number of values written (<= capacity). */
 int wspr_last_timings(double *ms, int capacity);
 /* Worker threads of the library's host pools alive in this process (the threads that call into the library are
@@ -537,6 +540,78 @@ typedef struct {
 int wspr_block_demod_batch(const float *idat, const float *qdat, int nseg, int samples, size_t seg_stride,
                            const wspr_block_item *items, int n, unsigned char *symbols);
 int wspr_set_block_detection(int maxblock);
+/* A Doppler-spread figure per spot (kernel K11): how wide the received carrier is once the decode's own modulation has
+ * been wiped off -- what FST4W reports with every decode and what users of WSPR spots as an ionospheric probe ask for.
+ * The reference has no such figure, so the definition is this library's own (rtlsdr-wsprd_amd/csrc/kernels/spread.h;
+ * tests/helpers/spread_check.c is its serial form).  For one job (seg, f0, shift, drift, symbols[162]) over a row of np
+ * samples:
+ *   1. Phase: phi is the synthesiser's recurrence as stated at wspr_synth_tx above -- phi = 0.0, and for symbol i, sample
+ *      j: use phi, then phi += dphi_i, the same double expression with the same f0, drift and symbols; run as written,
+ *      not replaced by a prefix sum.  (sn, cs) = the synthesiser's sine and cosine of phi (synth_math.h).
+ *   2. Wipe: n = 256 i + j, k = shift + n: zr = (double)I[k]*cs + (double)Q[k]*sn, zi = (double)Q[k]*cs - (double)I[k]*sn,
+ *      unfused doubles; both are zero where k < 0 or k >= np.
+ *   3. Block sums: y[b], b = 0 .. 1295 = the sum of z over samples 32b .. 32b+31, each rail summed in double in sample
+ *      order from 0.0 and rounded once to float.
+ *   4. Spectrum: y zero-padded to 2 048 points, complex float32 radix-2 decimation-in-frequency transform with twiddles
+ *      (float)cos(2 pi m/2048), (float)(-sin(2 pi m/2048)) from the host libm, no fused multiply-add; P[j] = re*re + im*im
+ *      in float, separately rounded, j = -1024 .. 1023 the bin's signed index, bin j at j * D, D = 375/32/2048 Hz
+ *      (0.00572 Hz).
+ *   5. Width, in double, the order of additions part of the definition: bins in chunks of 16 consecutive j, a chunk
+ *      summed serially from 0.0 in rising j, chunk totals accumulated serially in rising chunk order.  nz = the 40 chunks
+ *      covering 640 <= |j| <= 959 (negative side first, from j = -959 and from j = 640) / 640.  Signal region j = -512 ..
+ *      511 (64 chunks), Q[j] = (double)P[j] - nz, tot = their accumulated total.  For q = 0.25, 0.5, 0.75: the first chunk
+ *      whose running total reaches q*tot, in it the first bin whose running sum reaches it, f_q = (j - 0.5 + (q*tot -
+ *      C_before)/Q[j]) * D.  w50 = (float)(f_75 - f_25): the width that holds the middle half of the carrier's power;
+ *      f50 = (float)f_50: the carrier's median offset from f0; ratio = (float)(largest P[j] of the signal region / nz).
+ *      valid = 1 if nz > 0, tot > 0, the three crossings exist and every number involved is finite; otherwise valid = 0
+ *      and the three floats are 0.
+ * wspr_set_arithmetic() does not touch any of this: it is a measurement, not part of the reference's arithmetic.
+ * What to expect: a Gaussian Doppler spectrum of standard deviation s gives w50 = 1.349 s, without bias down to the decode
+ * threshold; a carrier that is not spread at all gives the FLOOR of about 0.005 Hz (one bin of the 110.6 s the frame
+ * lasts).  ONE SPOT'S FIGURE SCATTERS BY TENS OF PERCENT (about +-30 %: that is 110 s of data, not the estimator), so
+ * use medians over spots.  Residual drift -- the decoder's drift is a whole number of Hz per frame -- or a wrong drift
+ * estimate widens the figure like a spread does; so does a wrong message (a false decode).
+ *
+ * wspr_spread_batch(): host rows as wspr_block_demod_batch() takes them and n jobs; out[i] receives job i's figures and
+ * echoes its f0 / shift / drift.  A frame may hang off either end of the row, or miss it (valid = 0).  Returns 0; -1 with
+ * NOTHING WRITTEN without a usable device, for samples outside 0 .. 45000, n < 0, a seg outside the batch, a symbol > 3,
+ * a non-finite f0 or drift, or |f0| + |drift|/2 > 1000 Hz; n == 0 does nothing.
+ *
+ * wspr_set_spread_estimate(): process-wide, 0 = off (the default), 1 = on; read once per decode call, on entry, like
+ * wspr_set_osd_depth().  Returns the previous value; any other argument changes nothing and returns -2.  While it is on,
+ * every decode that ADDS A SPOT (not a duplicate, not beyond the 100 uniques, not a loop exit) gets one job, built from
+ * the decode's refined freq / shift / drift and the symbols its message re-encodes to (valid = 0 if that fails), and run
+ * BEFORE that decode is subtracted: on the IQ the candidate was decoded from, the signal still in it and every earlier
+ * subtraction applied.  Spots, hash memory and IQ are what they are with the stage off.
+ *
+ * wspr_last_spreads(): the records of the calling thread's most recent decode call, in the layout of that call's `decodes`
+ * array -- entry s * max_results + i belongs to spot i of segment s (entry i for wspr_decode()); entries beyond
+ * n_results[s] are zero.  Returns the number of entries written (nseg * max_results; for wspr_decode(), *n_results), or -1
+ * if the stage was off for that call, the capacity is too small, or the call was of a family that does not record them.
+ * Recorded: wspr_decode(), wspr_decode_batch(), wspr_decode_batch_device(), wspr_decode_batch_hashed() (a segment decoded
+ * again reports its final round's figures) and wspr_selftest().  NOT recorded, -1 afterwards: wspr_decode_batch_node(),
+ * wspr_decode_batch_node_device(), wspr_session_decode() and wspr_session_decode_many(), and a call that failed.  The
+ * stage is OFF by default, and bench.py measures the default. */
+typedef struct {
+    int32_t seg;                    /* row of the batch */
+    float   f0;                     /* Hz relative to 1500 Hz, centre of the four tones */
+    int32_t shift;                  /* row index of the frame's first sample; may be negative */
+    float   drift;                  /* Hz over the frame */
+    unsigned char symbols[162];     /* channel symbols 0..3 of the message, e.g. from get_wspr_channel_symbols() */
+    unsigned char pad[2];
+} wspr_spread_item;
+typedef struct {
+    float   w50, f50, ratio;        /* Hz, Hz, peak over noise floor; all 0 unless valid */
+    int32_t valid;
+    float   f0;                     /* the job: what the figure was taken with */
+    int32_t shift;
+    float   drift;
+    int32_t pad;
+} wspr_spread;
+int wspr_spread_batch(const float *idat, const float *qdat, int nseg, int samples, size_t seg_stride,
+                      const wspr_spread_item *items, int n, wspr_spread *out);
+int wspr_set_spread_estimate(int on);
+int wspr_last_spreads(wspr_spread *spreads, int capacity);
 /* Library / device description, e.g. for bench logs. */
 const char *wspr_mi355x_version(void);
 int wspr_device_ready(void);        /* 1 if a HIP device and the kernels are usable */

@@ -131,6 +131,12 @@ def _bind(path):
     L.wspr_set_block_detection.restype = C.c_int
     L.wspr_block_demod_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
     L.wspr_block_demod_batch.restype = C.c_int
+    L.wspr_spread_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p]
+    L.wspr_spread_batch.restype = C.c_int
+    L.wspr_set_spread_estimate.argtypes = [C.c_int]
+    L.wspr_set_spread_estimate.restype = C.c_int
+    L.wspr_last_spreads.argtypes = [C.c_void_p, C.c_int]
+    L.wspr_last_spreads.restype = C.c_int
     L.wspr_synth_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int,
                                           C.c_void_p, C.c_void_p]
     L.wspr_synth_batch_device.restype = C.c_int
@@ -252,6 +258,47 @@ def block_demod(I, Q, items, library=None):
     if rc != 0:
         raise RuntimeError("wspr_block_demod_batch failed (rc %d: bad arguments, or no usable HIP device)" % rc)
     return sym
+
+
+# include/wspr_mi355x.h: wspr_spread_item (one job of wspr_spread_batch()) and wspr_spread (its result, and one record of
+# wspr_last_spreads())
+SPREAD_ITEM_DTYPE = np.dtype([("seg", "<i4"), ("f0", "<f4"), ("shift", "<i4"), ("drift", "<f4"), ("symbols", "u1", (NSYM,)),
+                              ("pad", "u1", (2,))])
+SPREAD_DTYPE = np.dtype([("w50", "<f4"), ("f50", "<f4"), ("ratio", "<f4"), ("valid", "<i4"), ("f0", "<f4"), ("shift", "<i4"),
+                         ("drift", "<f4"), ("pad", "<i4")])
+
+
+def set_spread_estimate(on, library=None):
+    """wspr_set_spread_estimate() of include/wspr_mi355x.h: 1 adds a Doppler-spread figure per spot to every later decode
+    call (read back with last_spreads()), 0 switches it off (the default).  Returns the previous value, or -2 (nothing
+    changed) for any other argument.  The product and the lab library each keep their own setting."""
+    return (library or lib()).wspr_set_spread_estimate(int(on))
+
+
+def spread_batch(I, Q, items, samples=None, library=None):
+    """wspr_spread_batch(): host rows [nseg, row length] of which `samples` count (default: all), and n jobs -- a numpy
+    array of SPREAD_ITEM_DTYPE.  Returns a SPREAD_DTYPE array [n]; raises if the library refuses the call."""
+    I = np.ascontiguousarray(I, dtype=np.float32)
+    Q = np.ascontiguousarray(Q, dtype=np.float32)
+    if I.ndim == 1:
+        I, Q = I[None, :], Q[None, :]
+    nseg, width = I.shape
+    it = np.ascontiguousarray(items, dtype=SPREAD_ITEM_DTYPE)
+    out = np.zeros(int(it.size), SPREAD_DTYPE)
+    rc = (library or lib()).wspr_spread_batch(_ptr(I), _ptr(Q), nseg, width if samples is None else int(samples), width,
+                                              _ptr(it), int(it.size), _ptr(out))
+    if rc != 0:
+        raise RuntimeError("wspr_spread_batch failed (rc %d: bad arguments, or no usable HIP device)" % rc)
+    return out
+
+
+def last_spreads(nseg, max_results, library=None):
+    """wspr_last_spreads() for a call of nseg segments and max_results spots each: a SPREAD_DTYPE array [nseg, max_results]
+    (entries beyond a segment's spots are zero), or None where the library answers -1 (stage off for that call, or a
+    call that does not record them)."""
+    out = np.zeros((int(nseg), int(max_results)), SPREAD_DTYPE)
+    n = (library or lib()).wspr_last_spreads(_ptr(out), int(out.size))
+    return out if n == out.size else None
 
 
 def get_wspr_channel_symbols(message):
@@ -398,7 +445,8 @@ TIMING_NAMES = (
     "cpu_ms_call", "cpu_ms_pass_start", "cpu_ms_build_wave", "cpu_ms_refine", "cpu_ms_ladder", "cpu_ms_books",
     "cpu_ms_subtract", "cpu_ms_finish", "message_cache_lookups", "message_cache_hits",
     "osd_ms", "osd_vectors", "osd_spots", "lag_pruned", "lag_exact_evals", "lag_fallbacks",
-    "block_ms", "block_vectors", "block2_decodes", "block3_decodes")
+    "block_ms", "block_vectors", "block2_decodes", "block3_decodes",
+    "spread_ms", "spread_jobs")
 
 
 def last_timings():

@@ -49,7 +49,18 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
     Context::note_slots_used(nslots);
     Context& c0 = Context::get();
     const int dev = c0.device(), lane = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
-              maxblock = wspr::call_maxblock();
+              maxblock = wspr::call_maxblock(), spread_on = wspr::call_spread();
+    // wspr_last_spreads(): the calling thread's record takes the layout of `decodes`; a revisit of the same layout keeps
+    // the entries of the segments it does not decode again.  The traced form does not record.
+    wspr::LastSpreads& last = wspr::last_spreads_of_thread();
+    wspr_spread* spread_rec = nullptr;
+    if (spread_on > 0 && !trace && max_results > 0) {
+        const bool keep = revisit && last.on && last.nseg == nseg && last.max_results == max_results;
+        if (!keep) last.rec.assign((size_t)nseg * (size_t)max_results, wspr_spread{});
+        last.nseg = nseg; last.max_results = max_results;
+        spread_rec = last.rec.data();
+    }
+    last.on = false;                                       // until this call has run to its end
     struct Share { int lo, hi; };
     std::vector<Share> share(nslots);
     for (int g = 0; g < nslots; ++g) share[g] = {(int)((long)nseg * g / nslots), (int)((long)nseg * (g + 1) / nslots)};
@@ -65,6 +76,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
                     wspr::ArithScope call_mode(arith);
                     wspr::OsdScope call_osd(osd_depth);
                     wspr::BlockScope call_block(maxblock);
+                    wspr::SpreadScope call_spread(spread_on);
                     if (hipSetDevice(dev) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
                     Context::bind_lane(lane);
                     fn(g, Context::slot(g));
@@ -81,6 +93,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
             for (int t : todo) if (t >= lo && t < hi) mine.push_back(t - lo);
             if (mine.empty()) return;
             reload(c, lo, mine);
+            c.set_spread_out(spread_rec ? spread_rec + (size_t)lo * max_results : nullptr);
             c.decode_again(hi - lo, samples, options, decodes + (size_t)lo * max_results, max_results, n_results + lo, mine, hb, lo);
         });
     };
@@ -88,6 +101,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
         on_slots([&](int g, Context& c) {
             const int lo = share[g].lo, hi = share[g].hi;
             load(c, lo, hi - lo);
+            c.set_spread_out(spread_rec ? spread_rec + (size_t)lo * max_results : nullptr);
             const int rc = c.decode_resident(hi - lo, samples, options, decodes + (size_t)lo * max_results, max_results, n_results + lo,
                                              [&c, &reload, lo](const std::vector<int>& segs) { reload(c, lo, segs); },
                                              trace ? trace + lo : nullptr, hb, lo);
@@ -113,6 +127,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
             const int lo = share[g].lo, hi = share[g].hi;
             c.store_host(idat + (size_t)lo * seg_stride, qdat + (size_t)lo * seg_stride, hi - lo, samples, seg_stride);
         });
+    last.on = spread_rec != nullptr;
     return 0;
 }
 
@@ -373,6 +388,9 @@ int wspr_decode(float* idat, float* qdat, int samples, struct decoder_options op
     const int rc = wspr_decode_batch(idat, qdat, 1, samples, (size_t)samples, options, tmp.data(), MAX_UNIQUES, &n, 1);
     for (int i = 0; i < n; ++i) decodes[i] = tmp[i];
     *n_results = n;
+    // wspr_last_spreads() follows the caller's array: entry i, n of them
+    wspr::LastSpreads& last = wspr::last_spreads_of_thread();
+    if (last.on && last.nseg == 1) { last.max_results = n < 0 ? 0 : n; last.rec.resize((size_t)last.max_results); }
     return rc < 0 ? rc : 0;
 }
 

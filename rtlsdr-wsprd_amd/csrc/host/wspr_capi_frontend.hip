@@ -217,6 +217,7 @@ const float* wspr_session_samples(const wspr_session* s, int buffer, int rail) {
 }
 
 int wspr_session_decode(wspr_session* s, int buffer, struct decoder_results* decodes, int* n_results) {
+    wspr::NoSpreadRecord no_record;
     if (!s || (buffer & ~1) != 0 || !n_results) return -1;
     *n_results = 0;
     if (!session_prepare(s, buffer)) return 0;
@@ -232,6 +233,7 @@ int wspr_session_decode(wspr_session* s, int buffer, struct decoder_results* dec
 // and only runs of consecutive sessions with equal options share a call (see `ordered` below).
 int wspr_session_decode_many(wspr_session* const* sessions, const int* buffers, int n, struct decoder_results* decodes,
                              int max_results, int* n_results, int* decoded) {
+    wspr::NoSpreadRecord no_record;
     if (!sessions || !buffers || n < 0 || !decodes || max_results < 1 || !n_results) return -1;
     wspr::ArithScope call_mode;            // one mode for every group of options this call decodes
     wspr::OsdScope call_osd;               // and one ordered-statistics depth

@@ -57,6 +57,7 @@ void wspr_shard_range(int nseg, int shard, int nshards, int* lo, int* hi) {
 int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size_t seg_stride,
                            struct decoder_options options, struct decoder_results* decodes, int max_results,
                            int* n_results, int ndevices) {
+    wspr::NoSpreadRecord no_record;
     const int count = wspr_device_count();
     if (count <= 0) {
         fprintf(stderr, "libwspr_mi355x: wspr_decode_batch_node: no HIP device visible (there is no CPU fallback)\n");
@@ -118,6 +119,7 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
 int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int src_device, int nseg, int samples,
                                   size_t seg_stride, struct decoder_options options, struct decoder_results* decodes,
                                   int max_results, int* n_results, int ndevices) {
+    wspr::NoSpreadRecord no_record;
     const int count = wspr_device_count();
     if (count <= 0 || src_device < 0 || src_device >= count) {
         fprintf(stderr, "libwspr_mi355x: wspr_decode_batch_node_device: no such source device %d (%d visible)\n", src_device, count);

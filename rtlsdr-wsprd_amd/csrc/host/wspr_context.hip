@@ -197,10 +197,10 @@ size_t Context::release_buffers() {
                               &c.symbuf, &c.rmsbuf, &c.jobs, &c.subscratch, &c.nvalid, &c.decscratch, &c.tabs, &c.pw, &c.pwfreq, &c.lagprune,
                               &c.lists, &c.scrsync, &c.psavg, &c.densein, &c.fz_sym, &c.fz_off, &c.fz_ret, &c.fz_cyc, &c.fz_met, &c.fz_max,
                               &c.fz_dat, &c.fz_steps, &c.fz_pool, &c.streamraw, &c.streamstate, &c.synthtx, &c.synthoff, &c.synthfirst,
-                              &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out})
+                              &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out, &c.spr_tw, &c.spr_jobs, &c.spr_ckpt, &c.spr_out})
                 freed += b->release();
             for (PinBuf* b : {&c.h_npk, &c.h_cand, &c.h_items, &c.h_sync, &c.h_sym, &c.h_rms, &c.h_jobs, &c.h_jobs2, &c.h_seglist,
-                              &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
+                              &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_sprjobs, &c.h_sprout, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
                 b->release();
             c.stage_samples[0] = c.stage_samples[1] = 0;
             free(c.hash_arena);
@@ -528,6 +528,54 @@ int Context::block_demod_batch(const float* I, const float* Q, int nseg, int sam
     load_host(I, Q, nseg, samples, stride);
     return block_resident(hyps, n, samples, symbols, nullptr, nullptr);
 }
+
+// K11 (the definition in kernels/spread.h).  The twiddle table is built on first use: a process that never asks for the
+// figure allocates nothing for it.
+const float* Context::spread_twiddle_table() {
+    Impl& c = *d;
+    if (!c.spr_tw.p) {
+        static const std::vector<float> host = [] { std::vector<float> t(2 * spread::kTwiddles); spread::spread_twiddles(t.data()); return t; }();
+        float* p = static_cast<float*>(c.spr_tw.need(host.size() * sizeof(float)));
+        HIP_OK(hipMemcpy(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return c.spr_tw.as<float>();
+}
+
+// Queues K11 over n jobs on the working rows: jobs -> pinned staging -> device, the kernels, the 16-byte results back into
+// pinned memory.  Nothing waits; the returned pointer holds n x 4 words once the stream has passed this point.
+const uint32_t* Context::spread_enqueue(const SubJob* jobs, int n, int samples) {
+    Impl& c = *d;
+    const float* tw = spread_twiddle_table();
+    SubJob* hj = static_cast<SubJob*>(c.h_sprjobs.need((size_t)n * sizeof(SubJob)));
+    memcpy(hj, jobs, (size_t)n * sizeof(SubJob));
+    SubJob* dj = static_cast<SubJob*>(c.spr_jobs.need((size_t)n * sizeof(SubJob)));
+    double* ck = static_cast<double*>(c.spr_ckpt.need(spread_checkpoint_doubles(n) * sizeof(double)));
+    void* dout = c.spr_out.need((size_t)n * 16);
+    uint32_t* hout = static_cast<uint32_t*>(c.h_sprout.need((size_t)n * 16));
+    upload(dj, hj, (size_t)n * sizeof(SubJob), c.stream);
+    launch_spread(c.iqI.as<float>(), c.iqQ.as<float>(), std::max(0, std::min(samples, (int)kMaxSamples)), dj, n, ck, tw, dout, c.stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(hout, dout, (size_t)n * 16, hipMemcpyDeviceToHost, c.stream));
+    return hout;
+}
+
+// K11 over host rows (wspr_spread_batch): the caller has validated the items against nseg
+int Context::spread_batch(const float* I, const float* Q, int nseg, int samples, size_t stride, const wspr_spread_item* items,
+                          int n, wspr_spread* out) {
+    static_assert(sizeof(wspr_spread_item) == sizeof(SubJob) && sizeof(wspr_spread) == 32, "wspr_spread_item is the kernel's job");
+    if (samples > 0) load_host(I, Q, nseg, samples, stride);
+    const uint32_t* words = spread_enqueue(reinterpret_cast<const SubJob*>(items), n, samples);
+    sync();
+    for (int i = 0; i < n; ++i) {
+        wspr_spread r;
+        memcpy(&r, words + (size_t)4 * i, 16);
+        r.f0 = items[i].f0; r.shift = items[i].shift; r.drift = items[i].drift; r.pad = 0;
+        out[i] = r;
+    }
+    return 0;
+}
+
+void Context::set_spread_out(wspr_spread* out) { d->spread_out = out; }
 
 void Context::subtract_single(float* id, float* qd, long np, float f0, int shift, float drift,
                               const unsigned char* sym) {

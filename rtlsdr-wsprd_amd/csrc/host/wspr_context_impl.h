@@ -22,6 +22,7 @@
 
 #include "wspr_message.h"
 #include "../kernels/osd.h"
+#include "../kernels/spread.h"
 
 namespace wspr {
 
@@ -226,6 +227,7 @@ struct SegBook {                 // host bookkeeping of one segment across passe
     SparseHashTable hash;        // the segment's hash memory (cleared when the batch ends); usehashtable: flat arena / HashBatch
     std::vector<int> dirty;      // hash slots written in the flat arena (single call with usehashtable)
     std::vector<decoder_results> spots;   // every unique spot, in decode order (the reference's 100 at most)
+    std::vector<wspr_spread> spreads;     // wspr_set_spread_estimate(1): the figure of each, same order (else empty)
 };
 
 struct Context::Impl {
@@ -252,6 +254,9 @@ struct Context::Impl {
     PinBuf h_osd;                    // K9's results on their way to the host
     DevBuf blk_hyp, blk_out;         // K10: the hypotheses, and [sync | rms | symbols] of each
     PinBuf h_blk;                    // ... on their way to the host
+    DevBuf spr_tw, spr_jobs, spr_ckpt, spr_out;   // K11: twiddles (built on first use), jobs, phase checkpoints, 4 words per job
+    PinBuf h_sprjobs, h_sprout;      // ... the jobs on their way up, the results on their way down
+    wspr_spread* spread_out = nullptr;   // where the current call's records go (the layout of its `decodes`), or null
     PinBuf h_stage[2];
     PinBuf h_streamraw, h_streamstate, h_streamout;   // many receivers' callbacks at once (decimate_stream_many)
     hipEvent_t ev_stage[2] = {nullptr, nullptr};

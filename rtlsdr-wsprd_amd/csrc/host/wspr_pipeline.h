@@ -72,6 +72,33 @@ struct BlockScope {
     BlockScope& operator=(const BlockScope&) = delete;
 };
 
+// wspr_set_spread_estimate(): process-wide, 0 off, 1 on.  Read ONCE per call, on entry, and handed to the threads a call
+// starts for itself, exactly as the settings above.
+std::atomic<int>& spread_setting();
+int& call_spread_slot();                                  // thread-local: the current call's value, -1 outside a call
+inline int call_spread() { const int m = call_spread_slot(); return m < 0 ? spread_setting().load() : m; }
+struct SpreadScope {
+    bool owner;
+    SpreadScope() : owner(call_spread_slot() < 0) { if (owner) call_spread_slot() = spread_setting().load(); }
+    explicit SpreadScope(int on) : owner(call_spread_slot() < 0) { if (owner) call_spread_slot() = on; }
+    ~SpreadScope() { if (owner) call_spread_slot() = -1; }
+    SpreadScope(const SpreadScope&) = delete;
+    SpreadScope& operator=(const SpreadScope&) = delete;
+};
+// The records wspr_last_spreads() hands back: the calling thread's most recent decode call's, in the layout of that
+// call's `decodes` array.  on = the call ran with the stage on and is of a family that records them.
+struct LastSpreads {
+    bool on = false;
+    int nseg = 0, max_results = 0;
+    std::vector<wspr_spread> rec;
+};
+LastSpreads& last_spreads_of_thread();
+// An entry point of a family that does not record them (node-level calls, receiver sessions): whatever batch calls it
+// made on the calling thread, wspr_last_spreads() answers -1 after it.
+struct NoSpreadRecord {
+    ~NoSpreadRecord() { last_spreads_of_thread().on = false; }
+};
+
 // The values of wspr_last_timings(), in the order include/wspr_mi355x.h documents (that order is ABI; the Python
 // wrapper's TIMING_NAMES repeats it).  A new value goes at the end, here and in both of those.
 enum TimingSlot : int {
@@ -84,6 +111,7 @@ enum TimingSlot : int {
     kTmOsdMs, kTmOsdVectors, kTmOsdSpots,
     kTmLagPruned, kTmLagExactEvals, kTmLagFallbacks,
     kTmBlockMs, kTmBlockVectors, kTmBlock2Decodes, kTmBlock3Decodes,
+    kTmSpreadMs, kTmSpreadJobs,
     kTimingSlots
 };
 // A batch runs on several pipelines at once and each keeps its own values; wspr_last_timings() folds them.  The stage
@@ -91,7 +119,7 @@ enum TimingSlot : int {
 // from it on is SUMMED -- the counts, and the CPU times kTmCpuMs* as well (CPU time spent on different threads adds
 // up; the public header says "summed over the slots").
 constexpr int kTimingFirstSummed = kTmFanoCalls;
-static_assert(kTimingSlots == 36 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
+static_assert(kTimingSlots == 38 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
 
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt
@@ -199,6 +227,13 @@ public:
                        const unsigned char** d_symbols = nullptr);
     int block_demod_batch(const float* I, const float* Q, int nseg, int samples, size_t stride, const BlockHyp* hyps, int n,
                           unsigned char* symbols);
+    // K11 (k11_spread.hip; the definition in kernels/spread.h): the figure of n jobs over host rows; on the working rows,
+    // queued without a wait (n x 4 words in pinned memory once the stream has passed); where a decode call's records go
+    int spread_batch(const float* I, const float* Q, int nseg, int samples, size_t stride, const wspr_spread_item* items, int n,
+                     wspr_spread* out);
+    const uint32_t* spread_enqueue(const SubJob* jobs, int n, int samples);
+    const float* spread_twiddle_table();
+    void set_spread_out(wspr_spread* out);
     int bench_decimate(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int iters, double* ms);
     int decimate_device(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int normalise,
                         int* h_nout, DecimState* d_states = nullptr);

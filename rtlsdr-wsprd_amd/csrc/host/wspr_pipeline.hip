@@ -224,6 +224,19 @@ int& call_block_slot() {
     return m;
 }
 
+std::atomic<int>& spread_setting() {
+    static std::atomic<int> v{0};
+    return v;
+}
+int& call_spread_slot() {
+    thread_local int m = -1;
+    return m;
+}
+LastSpreads& last_spreads_of_thread() {
+    thread_local LastSpreads l;
+    return l;
+}
+
 std::atomic<unsigned>& fano_fast_budget() {
     static std::atomic<unsigned> v{[] { const char* e = getenv("WSPR_FANO_FAST"); return e ? (unsigned)atoi(e) : 10000u; }()};
     return v;
@@ -338,6 +351,17 @@ struct Context::DecodeRun {
     const int maxblock = call_maxblock();
     std::vector<unsigned char> by_block;
     std::atomic<long> n_block_decodes[2] = {{0}, {0}};   // consumed decodes by block size 2 and 3
+    // wspr_set_spread_estimate() of this call.  keep_books() leaves the wave's jobs here (one per decode that added a
+    // spot) with the place of each result among the segment's spots; launch_spreads() queues them ahead of the wave's
+    // subtraction, collect_spreads() files the results once the stream has passed them.
+    const bool spread_on = call_spread() > 0;
+    struct SpreadSlot { int seg, spot; };
+    std::vector<SubJob> spr_jobs;
+    std::vector<SpreadSlot> spr_slots, spr_flight;
+    const uint32_t* spr_words = nullptr;      // results of the jobs in flight (pinned), valid after a wait on the stream
+    hipEvent_t spr_done = nullptr;
+    int spr_def_top = -1;                     // c.n_def right after the stage's deferred event pair was recorded
+    ~DecodeRun() { if (spr_done) (void)hipEventDestroy(spr_done); }
 
     // one Fano attempt on a soft-symbol vector in transmission order (wsprd.c:759-761)
     int fano_attempt(const unsigned char* tx_sym, unsigned* cycles, unsigned char* data11) const {
@@ -422,6 +446,8 @@ struct Context::DecodeRun {
     void osd_rescue(std::vector<WaveItem>& wave);
     std::vector<SubJob> keep_books(std::vector<WaveItem>& wave);
     void subtract(const std::vector<SubJob>& jobs);
+    void launch_spreads();
+    void collect_spreads();
     void finish(const std::vector<int>& active0, int* n_results);
     void clear_hash(const std::vector<int>& segs);
 };
@@ -947,6 +973,8 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
     const int ngroups = (int)group_start.size() - 1;
     std::vector<SubJob> job_of(nw);
     std::vector<char> has_job(nw, 0);
+    std::vector<SubJob> spr_of(spread_on ? nw : 0);
+    std::vector<int> spr_spot(spread_on ? nw : 0, -1);
     c.pool->run(ngroups, [&](int g) {
       const int sg = wave[group_start[g]].seg;
       bool cut = false;
@@ -1045,12 +1073,40 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
             copy_text(o->loc, sizeof o->loc, loc);
             copy_text(o->pwr, sizeof o->pwr, pwr);
         }
+        if (spread_on) {
+            // the figure is taken with the decode's own parameters and the symbols its message re-encodes to -- against a
+            // table that takes no stores and logs no look-ups: the hash memory is what it is without the stage
+            struct NoStores : HashTable {
+                HashTable& t;
+                explicit NoStores(HashTable& t_) : t(t_) {}
+                const char* call_at(int slot) override { return t.peek(slot); }
+                const char* peek(int slot) override { return t.peek(slot); }
+                void put(int, const char*, const char*) override {}
+            } quiet(tab);
+            wspr_spread sp{};
+            sp.f0 = w.fine.freq; sp.shift = w.fine.shift; sp.drift = w.fine.drift;
+            SubJob jb{};
+            const bool have = has_job[i] ? (memcpy(jb.sym, job_of[i].sym, kNSymD), true)
+                                         : channel_symbols(call_loc_pow, quiet, jb.sym) != 0;
+            if (have && std::isfinite(w.fine.freq) && std::isfinite(w.fine.drift) &&
+                std::fabs((double)w.fine.freq) + std::fabs((double)w.fine.drift) / 2.0 <= kSynthMaxHz) {
+                jb.seg = s; jb.f0 = w.fine.freq; jb.shift = w.fine.shift; jb.drift = w.fine.drift;
+                spr_of[i] = jb;
+                spr_spot[i] = (int)bk.spreads.size();
+            }
+            bk.spreads.push_back(sp);
+        }
       }
       if (lockstep) win[sg] = cut ? 1 : std::min(64, 2 * win[sg]);
     });
     std::vector<SubJob> jobs;
     for (int i = 0; i < nw; ++i) if (has_job[i]) jobs.push_back(job_of[i]);
     c.n_subjobs += (long)jobs.size();
+    if (spread_on) {
+        spr_jobs.clear(); spr_slots.clear();
+        for (int i = 0; i < nw; ++i)
+            if (spr_spot[i] >= 0) { spr_jobs.push_back(spr_of[i]); spr_slots.push_back(SpreadSlot{wave[i].seg, spr_spot[i]}); }
+    }
     c.t_ms[kTmHostBookkeepingMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_b0).count();
     return jobs;
 }
@@ -1081,6 +1137,41 @@ void Context::DecodeRun::subtract(const std::vector<SubJob>& jobs) {
     HIP_OK(hipGetLastError());
 }
 
+// GPU: the spread figure of every decode of this wave that added a spot, queued BEFORE the wave's subtraction: it is taken
+// on the IQ the candidate was decoded from, that signal still in it and every earlier subtraction applied.  No host wait:
+// the results come down behind the kernels and are filed by collect_spreads().
+void Context::DecodeRun::launch_spreads() {
+    if (!spread_on) return;
+    collect_spreads();                                     // one batch in flight: its pinned words are about to be reused
+    if (spr_jobs.empty()) return;
+    const int nj = (int)spr_jobs.size();
+    const int slot_ev = c.n_def < Impl::kDeferred ? c.n_def : -1;
+    if (slot_ev >= 0) HIP_OK(hipEventRecord(c.ev_def[slot_ev][0], c.stream));
+    spr_words = ctx.spread_enqueue(spr_jobs.data(), nj, samples);
+    if (slot_ev >= 0) {
+        HIP_OK(hipEventRecord(c.ev_def[slot_ev][1], c.stream));
+        c.def_acc[slot_ev] = &c.t_ms[kTmSpreadMs];
+        c.n_def = slot_ev + 1;
+    }
+    spr_def_top = slot_ev >= 0 ? c.n_def : -1;
+    if (!spr_done) HIP_OK(hipEventCreateWithFlags(&spr_done, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(spr_done, c.stream));
+    spr_flight.swap(spr_slots);
+    c.t_ms[kTmSpreadJobs] += (double)nj;
+    spr_jobs.clear(); spr_slots.clear();
+}
+
+void Context::DecodeRun::collect_spreads() {
+    if (spr_flight.empty()) return;
+    host_wait(spr_done);                                   // usually long passed: a wave's own waits lie in between
+    if (c.n_def == spr_def_top) c.resolve_deferred();      // nothing was queued behind the stage's own event pair: all have passed
+    for (size_t i = 0; i < spr_flight.size(); ++i) {
+        wspr_spread& sp = book[spr_flight[i].seg].spreads[(size_t)spr_flight[i].spot];
+        memcpy(&sp, spr_words + 4 * i, 16);                // w50, f50, ratio, valid; f0 / shift / drift are the job's
+    }
+    spr_flight.clear();
+}
+
 // results strongest first (wsprd.c:827; stable like glibc's merge sort) -- ALL unique spots of the segment
 // are ranked, then the strongest max_results are handed out (a caller with a short array loses the weakest
 // spots, never a strong one that happened to decode late); hash slots written by the batch are cleared again
@@ -1090,8 +1181,29 @@ void Context::DecodeRun::clear_hash(const std::vector<int>& segs) {
 }
 
 void Context::DecodeRun::finish(const std::vector<int>& active0, int* n_results) {
+    if (spread_on) collect_spreads();
     for (int s : active0) {
         SegBook& bk = book[s];
+        if (spread_on) {
+            // the same stable permutation and the same cut for the spots and their figures
+            const int m = (int)bk.spots.size();
+            std::vector<int> order(m);
+            for (int i = 0; i < m; ++i) order[i] = i;
+            std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bk.spots[a].snr > bk.spots[b].snr; });
+            std::vector<decoder_results> sp(m);
+            std::vector<wspr_spread> fig(m);
+            for (int i = 0; i < m; ++i) { sp[i] = bk.spots[order[i]]; fig[i] = bk.spreads[order[i]]; }
+            bk.spots.swap(sp); bk.spreads.swap(fig);
+            const int n = std::min(m, max_results);
+            if (n > 0) memcpy(out + (size_t)s * max_results, bk.spots.data(), (size_t)n * sizeof(decoder_results));
+            if (c.spread_out) {
+                wspr_spread* so = c.spread_out + (size_t)s * max_results;
+                if (n > 0) memcpy(so, bk.spreads.data(), (size_t)n * sizeof(wspr_spread));
+                if (max_results > n) memset(so + n, 0, (size_t)(max_results - n) * sizeof(wspr_spread));
+            }
+            n_results[s] = n;
+            continue;
+        }
         std::stable_sort(bk.spots.begin(), bk.spots.end(),
                          [](const decoder_results& a, const decoder_results& b) { return a.snr > b.snr; });
         const int n = std::min((int)bk.spots.size(), max_results);
@@ -1110,7 +1222,7 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
                          const FanoMemo* memo, wspr_trace* trace, HashBatch* hb, int hb_off) {
     for (int s : active0) n_results[s] = 0;
     DecodeRun run(*this, nseg, samples, opt, out, max_results, fast, pend);
-    for (int s : active0) { SegBook& b = run.book[s]; b.uniques = 0; b.dirty.clear(); b.hash.entries.clear(); b.spots.clear(); }
+    for (int s : active0) { SegBook& b = run.book[s]; b.uniques = 0; b.dirty.clear(); b.hash.entries.clear(); b.spots.clear(); b.spreads.clear(); }
     run.memo = memo;
     run.trace = trace;
     run.hb = hb;
@@ -1147,6 +1259,7 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
             if (run.osd_depth >= 0) { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.osd_rescue(wave); }
             std::vector<SubJob> jobs;
             { CpuSpan sp(&d->t_ms[kTmCpuMsBooks]); jobs = run.keep_books(wave); }
+            if (run.spread_on) { CpuSpan sp(&d->t_ms[kTmCpuMsSubtract]); run.launch_spreads(); }
             { CpuSpan sp(&d->t_ms[kTmCpuMsSubtract]); run.subtract(jobs); }
         }
     }

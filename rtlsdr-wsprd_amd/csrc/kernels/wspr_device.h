@@ -200,6 +200,12 @@ struct BlockHyp {
 void launch_block_demod(const float* dI, const float* dQ, int samples, const BlockHyp* hyps, int nhyp,
                         unsigned char* sym_out, float* rms_out, float* sync_out, const DeviceTables& t, hipStream_t st,
                         int arith);
+// K11, the Doppler-spread figure (k11_spread.hip; the definition in spread.h).  A job is a SubJob -- wspr_spread_item of the
+// public header has its layout.  ckpt: spread_checkpoint_doubles(n) doubles of scratch, tw: the 2 x 1 024 floats of
+// spread::spread_twiddles() in device memory, out: n x 4 words (w50, f50, ratio as floats, valid), 16-byte aligned.
+size_t spread_checkpoint_doubles(int n);
+void launch_spread(const float* dI, const float* dQ, int samples, const SubJob* jobs, int n, double* ckpt, const float* tw,
+                   void* out, hipStream_t st);
 // K8, the signal synthesiser (k8_synth.hip; arithmetic in synth_math.h).  SynthTx is wspr_synth_tx of the public header.
 struct SynthTx {
     int32_t seg;
