@@ -343,15 +343,19 @@ int wspr_format_wsprnet_url(const struct decoder_results *r, const struct decode
 
 /* ---- the reference's other decoder entry points, GPU-backed ---------------- */
 /* Replaces sync_and_demodulate(), reference wsprd/wsprd.h:76-91 (GPU-backed).  symfac is honoured (mode 2,
- * wsprd.c:250); the decoder itself always passes 50. */
+ * wsprd.c:250); the decoder itself always passes 50.
+ * np (here, in subtract_signal() and in subtract_signal2()): a record holds at most 45 000 samples, as in the reference's
+ * decoder.  np above 45 000 is treated as 45 000: id[k] and qd[k] with k >= 45 000 are neither read nor written. */
 void sync_and_demodulate(float *id, float *qd, long np, unsigned char *symbols, float *freq,
                          int ifmin, int ifmax, float fstep, int *shift, int lagmin, int lagmax,
                          int lagstep, float *drift, int symfac, float *sync, int mode);
 /* Replaces subtract_signal(), reference wsprd/wsprd.h:83-89 / wsprd.c:263-312 (symbol-by-symbol subtraction;
- * declared by the reference's header, never called by its decoder; GPU-backed). */
+ * declared by the reference's header, never called by its decoder; GPU-backed).  np above 45 000 is treated as 45 000 (see
+ * sync_and_demodulate()). */
 void subtract_signal(float *id, float *qd, long np, float f0, int shift, float drift,
                      const unsigned char *channel_symbols);
-/* Replaces subtract_signal2(), reference wsprd/wsprd.h:99-105 (GPU-backed). */
+/* Replaces subtract_signal2(), reference wsprd/wsprd.h:99-105 (GPU-backed).  np above 45 000 is treated as 45 000: samples
+ * behind it are neither read nor written (see sync_and_demodulate()). */
 void subtract_signal2(float *id, float *qd, long np, float f0, int shift, float drift,
                       const unsigned char *channel_symbols);
 /* Timing of the stages of the most recent batch call, milliseconds (HIP events on the library's

@@ -76,11 +76,7 @@ Context::Context(int nslots) : d(new Impl) {
     }
     tw[0] = make_float2(1.0f, 0.0f);
     tw[128] = make_float2(0.0f, -1.0f);
-    float norm = 0.0f;                                                               // wsprd.c:353-368
-    for (int i = 0; i < kLpfTaps; ++i) { lpf[i] = sinf(M_PI * (float)i / (float)(kLpfTaps - 1)); norm = norm + lpf[i]; }
-    for (int i = 0; i < kLpfTaps; ++i) lpf[i] = lpf[i] / norm;
-    part[0] = 0.0f;
-    for (int i = 1; i < kLpfTaps; ++i) part[i] = part[i - 1] + lpf[i];
+    subtract_lpf_tables(lpf.data(), part.data());
     for (int idt = 0; idt < kMaxLags; ++idt) {                                       // wsprd.c:742-744
         int ii = (idt + 1) / 2;
         if (idt % 2 == 1) ii = -ii;
@@ -461,6 +457,7 @@ void Context::demod_single(float* id, float* qd, long np, unsigned char* symbols
                            int ifmax, float fstep, int* shift, int lagmin, int lagmax, int lagstep,
                            float* drift, float* sync, int mode, int symfac) {
     Impl& c = *d;
+    // the kernels see the clamped count as well: a working row holds kIqStride floats, and only k < np guards their accesses
     const int samples = (int)std::min<long>(np, kMaxSamples);
     load_host(id, qd, 1, samples, (size_t)samples);
     FineState f{};
@@ -473,18 +470,18 @@ void Context::demod_single(float* id, float* qd, long np, unsigned char* symbols
     if (mode == 0) {
         const int nl = (lagmax - lagmin) / lagstep + 1;
         float* d_sync = static_cast<float*>(c.syncbuf.need((size_t)nl * 4));
-        launch_demod(wi, wq, (int)np, d_items, 1, 0, nl, lagstep, 0, 0.0f, nullptr, 0.0f, d_sync, nullptr, nullptr, c.tab, c.stream, 50, call_arith());
+        launch_demod(wi, wq, samples, d_items, 1, 0, nl, lagstep, 0, 0.0f, nullptr, 0.0f, d_sync, nullptr, nullptr, c.tab, c.stream, 50, call_arith());
         launch_pick_lag(d_items, 1, d_sync, nl, lagstep, c.stream);
     } else if (mode == 1) {
         const int nf = ifmax - ifmin + 1;
         float* d_sync = static_cast<float*>(c.syncbuf.need((size_t)nf * 4));
-        launch_demod(wi, wq, (int)np, d_items, 1, 1, nf, lagstep, ifmin, fstep, nullptr, 0.0f, d_sync, nullptr, nullptr, c.tab, c.stream, 50, call_arith());
+        launch_demod(wi, wq, samples, d_items, 1, 1, nf, lagstep, ifmin, fstep, nullptr, 0.0f, d_sync, nullptr, nullptr, c.tab, c.stream, 50, call_arith());
         launch_pick_freq(d_items, 1, d_sync, nf, ifmin, fstep, c.stream, call_arith());
     } else {
         float* d_sync = static_cast<float*>(c.syncbuf.need(4));
         unsigned char* d_sym = static_cast<unsigned char*>(c.symbuf.need(kNSymD));
         float* d_rms = static_cast<float*>(c.rmsbuf.need(4));
-        launch_demod(wi, wq, (int)np, d_items, 1, 2, 1, lagstep, 0, 0.0f, c.t_jitter.as<int>(), -INFINITY, d_sync, d_sym, d_rms, c.tab, c.stream, symfac, call_arith());
+        launch_demod(wi, wq, samples, d_items, 1, 2, 1, lagstep, 0, 0.0f, c.t_jitter.as<int>(), -INFINITY, d_sync, d_sym, d_rms, c.tab, c.stream, symfac, call_arith());
         float s2 = 0;
         HIP_OK(hipMemcpyAsync(&s2, d_sync, 4, hipMemcpyDeviceToHost, c.stream));
         HIP_OK(hipMemcpyAsync(symbols, d_sym, kNSymD, hipMemcpyDeviceToHost, c.stream));
@@ -588,7 +585,7 @@ void Context::subtract_single(float* id, float* qd, long np, float f0, int shift
     SubJob* dj = static_cast<SubJob*>(c.jobs.need(sizeof jb));
     upload(dj, &jb, sizeof jb, c.stream);
     float* scratch = static_cast<float*>(c.subscratch.need(subtract_scratch_floats(1) * 4));
-    launch_subtract(c.iqI.as<float>(), c.iqQ.as<float>(), (int)np, dj, 1, scratch, c.tab, c.stream, call_arith());
+    launch_subtract(c.iqI.as<float>(), c.iqQ.as<float>(), samples, dj, 1, scratch, c.tab, c.stream, call_arith());
     store_host(id, qd, 1, samples, (size_t)samples);
 }
 

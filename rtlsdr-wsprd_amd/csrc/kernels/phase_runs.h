@@ -227,8 +227,8 @@ WSPR_PR_HD float phase_join(int32_t m, int e) {
 // The decomposition of phase_runs_build() formed chain by chain: `width` symbols are probed at once (a wave's
 // lanes on the device; a loop here), the leading ones that pass become one run each with prefix-summed
 // significands, the first that fails is walked serially.  Same tables as phase_runs_build(), bit for bit
-// (tests/test_phase_runs.py compares them); this scalar form is what the tests run and what documents
-// sub_runs_kernel's wave form.
+// (tests/test_phase_runs.py compares them); this scalar form documents sub_runs_wave_kernel's wave form, whose own
+// table tests/test_gpu_k7_table.py dumps and holds against phase_runs_build()'s.
 template <class DphiOf>
 WSPR_PR_HD int phase_runs_build_chained(const DphiOf& dphi_of, int nsym, int sps, PhaseRun* runs, int max_runs,
                                         uint16_t* first_run, float* sym_phi, int width) {

@@ -12,6 +12,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
 
@@ -166,6 +167,16 @@ void launch_pick_lag(FineState* items, int nitems, const float* sync_in, int nla
                      const unsigned long long* mask = nullptr);
 void launch_pick_freq(FineState* items, int nitems, const float* sync_in, int nfreq, int ifmin,
                       float fstep, hipStream_t st, int arith);
+// The subtraction's low-pass taps and their running sums as DeviceTables holds them (lpf[kLpfTaps], lpf_part[kLpfTaps]),
+// computed with the host libm exactly as the reference does, wsprd.c:353-368.  The context uploads these; so does
+// tools/subtract_check.hip.
+inline void subtract_lpf_tables(float* lpf, float* part) {
+    float norm = 0.0f;
+    for (int i = 0; i < kLpfTaps; ++i) { lpf[i] = sinf(M_PI * (float)i / (float)(kLpfTaps - 1)); norm = norm + lpf[i]; }
+    for (int i = 0; i < kLpfTaps; ++i) lpf[i] = lpf[i] / norm;
+    part[0] = 0.0f;
+    for (int i = 1; i < kLpfTaps; ++i) part[i] = part[i - 1] + lpf[i];
+}
 size_t subtract_scratch_floats(int njobs);
 void launch_subtract(float* dI, float* dQ, int samples, const SubJob* jobs, int njobs,
                      float* scratch /* subtract_scratch_floats(njobs) */, const DeviceTables& t, hipStream_t st,

@@ -52,3 +52,33 @@ extern "C" long phase_runs_chained_diff(const float* dphi, int nsym, int sps_log
     }
     return bad;
 }
+
+// The serial builder's result in the layout of the device's PhaseTable (k7_subtract.hip): runs[kPhaseMaxRuns], sym_phi[nsym],
+// first_run[nsym + 2].  Entries the builder does not write are left as the caller set them; when the runs do not fit,
+// first_run[0] becomes 0xffff as on the device (and -1 is returned, else the number of runs).
+extern "C" int phase_runs_table(const float* dphi, int nsym, int sps_log2, wspr::PhaseRun* runs, float* sym_phi,
+                                uint16_t* first_run) {
+    const int nr = wspr::phase_runs_build([&](int i) { return dphi[i]; }, nsym, 1 << sps_log2, runs, wspr::kPhaseMaxRuns,
+                                          first_run, sym_phi);
+    if (nr < 0) first_run[0] = 0xffffu;
+    return nr;
+}
+
+// Every sample's phase from such a table, with the selection sub_fir_fused_kernel makes: the run that holds the sample
+// (phase_at), or phase_from_symbol when first_run[0] == 0xffff.  Returns the number of samples skipped because the table
+// names a run outside [0, kPhaseMaxRuns) or an empty range -- a table no builder may leave (phi_out keeps its value there).
+extern "C" long phase_table_eval(const wspr::PhaseRun* runs, const float* sym_phi, const float* dphi,
+                                 const uint16_t* first_run, int nsym, int sps_log2, float* phi_out) {
+    const int sps = 1 << sps_log2;
+    const bool dense = first_run[0] == 0xffffu;
+    long skipped = 0;
+    for (int i = 0; i < nsym; ++i) {
+        const bool usable = dense || (first_run[i] < first_run[i + 1] && first_run[i + 1] <= wspr::kPhaseMaxRuns);
+        for (int j = 0; j < sps; ++j) {
+            const int n = i * sps + j;
+            if (!usable) { ++skipped; continue; }
+            phi_out[n] = dense ? wspr::phase_from_symbol(sym_phi[i], dphi[i], j) : wspr::phase_at(runs, first_run, sps_log2, n);
+        }
+    }
+    return skipped;
+}
