@@ -142,6 +142,14 @@ def _bind(path):
     L.wspr_synth_batch_device.restype = C.c_int
     L.wspr_synth.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
     L.wspr_synth.restype = C.c_int
+    L.wspr_audio_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.wspr_audio_batch_device.restype = C.c_int
+    L.wspr_audio_to_iq.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.wspr_audio_to_iq.restype = C.c_int
+    L.wspr_audio_constants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wspr_audio_constants.restype = None
+    L.wspr_read_wav_file.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
+    L.wspr_read_wav_file.restype = C.c_size_t
     L.wspr_selftest.argtypes = [decoder_options, C.c_void_p]
     L.wspr_selftest.restype = C.c_int
     L.nhash.restype = C.c_uint32
@@ -341,6 +349,48 @@ def wspr_synth(items, noise_sigma=0.0, seed=0, flags=0, I=None, Q=None):
     if lib().wspr_synth(C.addressof(arr), len(items), noise_sigma, seed, flags, _ptr(I), _ptr(Q)) != 0:
         raise RuntimeError("wspr_synth failed (bad arguments, or no usable HIP device)")
     return I, Q
+
+
+AUDIO_RATE = 12000                 # include/wspr_mi355x.h: the 12 kHz audio front end (K12)
+AUDIO_MAX_SAMPLES = 1440000
+AUDIO_NTAPS = 511
+
+
+def audio_batch_device(d_pcm, pcm_stride, nsamp, nseg, d_i, d_q, normalise=0):
+    """wspr_audio_batch_device(): nseg records of nsamp int16 samples at the raw device pointer d_pcm (row stride pcm_stride
+    samples) into nseg device rows of wspr_iq_stride() floats at d_i / d_q.  Returns the library's code (0; -1 with nothing
+    written; -2 for nsamp > AUDIO_MAX_SAMPLES)."""
+    return lib().wspr_audio_batch_device(d_pcm, int(pcm_stride), int(nsamp), int(nseg), d_i, d_q, int(normalise))
+
+
+def audio_to_iq(pcm, normalise=0):
+    """wspr_audio_to_iq(): one record (int16, 12 000 Hz, the band at 1 500 Hz) into host rows of 45000 floats, through the
+    device.  Returns (I, Q, n_out); raises if the library refuses the call."""
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    I = np.zeros(NSAMPLES, np.float32)
+    Q = np.zeros(NSAMPLES, np.float32)
+    n_out = C.c_uint32(0)
+    rc = lib().wspr_audio_to_iq(_ptr(pcm), int(pcm.size), _ptr(I), _ptr(Q), C.addressof(n_out), int(normalise))
+    if rc != 0:
+        raise RuntimeError("wspr_audio_to_iq failed (rc %d: a record above 120 s, or no usable HIP device)" % rc)
+    return I, Q, int(n_out.value)
+
+
+def read_wav_file(filename, cap=AUDIO_MAX_SAMPLES):
+    """wspr_read_wav_file(): the samples (int16) of a 12 000 Hz 16-bit mono PCM WAV file, at most `cap`; an empty array on
+    any error or any other format.  Host code: needs no device."""
+    pcm = np.zeros(max(1, int(cap)), np.int16)
+    n = lib().wspr_read_wav_file(os.fsencode(filename), _ptr(pcm), int(cap))
+    return pcm[:n].copy()
+
+
+def audio_constants():
+    """wspr_audio_constants(): (taps_i[511], taps_q[511], input samples per output)."""
+    gi = np.zeros(AUDIO_NTAPS, np.float32)
+    gq = np.zeros(AUDIO_NTAPS, np.float32)
+    r = C.c_int(0)
+    lib().wspr_audio_constants(_ptr(gi), _ptr(gq), C.addressof(r))
+    return gi, gq, int(r.value)
 
 
 def wspr_selftest(options=None):

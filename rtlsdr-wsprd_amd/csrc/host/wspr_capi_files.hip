@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "wspr_pipeline.h"
+#include "wspr_wav.h"
 
 namespace {
 // RFC 3986 unreserved characters pass, everything else is %XX (what curl_easy_escape does)
@@ -84,6 +85,9 @@ int wspr_read_c2_file(const char* filename, float* I, float* Q, double* dial_hz)
     fclose(fd);
     return n;
 }
+
+// One slot of 12 000 Hz 16-bit mono audio (the parser, plain C++: wspr_wav.cpp)
+size_t wspr_read_wav_file(const char* filename, int16_t* pcm, size_t cap) { return wspr::read_wav_file(filename, pcm, cap); }
 
 // writeRawIQfile(), rtlsdr_wsprd.c:595-617: always 45000 complex samples, Q negated.
 int wspr_write_iq_file(const char* filename, const float* I, const float* Q) {

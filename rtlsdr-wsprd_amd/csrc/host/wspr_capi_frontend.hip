@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "wspr_capi_impl.h"
+#include "../kernels/audio_front.h"
 
 using wspr::Context;
 using namespace wspr::capi;
@@ -120,6 +121,64 @@ int wspr_decimate_u8(const uint8_t* iq, size_t nbytes, float* I, float* Q, uint3
         if (n_out) *n_out = (uint32_t)nout;
         return 0;
     } catch (const std::exception& e) { return fail("wspr_decimate_u8", e); }
+}
+
+// ---- K12, the 12 kHz audio front end (kernels/audio_front.h) ----------------------------------------------------------
+// (the texts name no macro: tests/test_abi.py limits the macro-style names the product binary carries)
+static int audio_args_bad(const char* where, const void* d_pcm, size_t pcm_stride, long long nsamp, int nseg, const void* d_i,
+                          const void* d_q) {
+    const char* why = nullptr;
+    if (nseg < 0 || nsamp < 0) why = "negative count";
+    else if (nsamp > AUDIO_FRONT_MAX_SAMPLES) {
+        fprintf(stderr, "libwspr_mi355x: %s: a record holds at most 1440000 samples (120 s); longer ones are refused, not cut\n", where);
+        return -2;
+    }
+    else if (nseg > 0 && (!d_pcm || (reinterpret_cast<uintptr_t>(d_pcm) & 15))) why = "d_pcm must be 16-byte aligned device memory";
+    else if (nseg > 0 && ((pcm_stride & 7) || pcm_stride < (size_t)nsamp)) why = "pcm_stride must be a multiple of 8 and at least nsamp";
+    else if (nseg > 0 && (!d_i || !d_q || ((reinterpret_cast<uintptr_t>(d_i) | reinterpret_cast<uintptr_t>(d_q)) & 15)))
+        why = "d_idat and d_qdat must be 16-byte aligned device rows";
+    if (why) { fprintf(stderr, "libwspr_mi355x: %s: %s\n", where, why); return -1; }
+    return 0;
+}
+
+int wspr_audio_batch_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, void* d_idat, void* d_qdat,
+                            int normalise) {
+    LaneTurn lane_turn;
+    try {
+        if (const int bad = audio_args_bad("wspr_audio_batch_device", d_pcm, pcm_stride, nsamp, nseg, d_idat, d_qdat)) return bad;
+        return Context::get().audio_device(d_pcm, pcm_stride, nsamp, nseg, (float*)d_idat, (float*)d_qdat, normalise);
+    } catch (const std::exception& e) { return fail("wspr_audio_batch_device", e); }
+}
+
+int wspr_audio_to_iq(const int16_t* pcm, size_t nsamp, float* I, float* Q, uint32_t* n_out, int normalise) {
+    LaneTurn lane_turn;
+    try {
+        if (nsamp > (size_t)AUDIO_FRONT_MAX_SAMPLES) return audio_args_bad("wspr_audio_to_iq", nullptr, 0, (long long)AUDIO_FRONT_MAX_SAMPLES + 1, 0, nullptr, nullptr);
+        if ((!pcm && nsamp) || !I || !Q) { fprintf(stderr, "libwspr_mi355x: wspr_audio_to_iq: no record, or no output rows\n"); return -1; }
+        Context& c = Context::get();
+        int16_t* d_pcm = c.audio_pcm(nsamp);
+        if (nsamp) HIP_TRY(hipMemcpy(d_pcm, pcm, nsamp * sizeof(int16_t), hipMemcpyHostToDevice));
+        float* wi = c.work_i(1);
+        float* wq = c.work_q(1);
+        const int rc = c.audio_device(d_pcm, (nsamp + 7) & ~(size_t)7, (int)nsamp, 1, wi, wq, normalise);
+        if (rc) return rc;
+        const size_t bytes = (size_t)wspr::kMaxSamples * sizeof(float);
+        std::vector<float> oi(wspr::kMaxSamples), oq(wspr::kMaxSamples);    // both rails arrive before either is handed over
+        HIP_TRY(hipMemcpy(oi.data(), wi, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(oq.data(), wq, bytes, hipMemcpyDeviceToHost));
+        std::memcpy(I, oi.data(), bytes);
+        std::memcpy(Q, oq.data(), bytes);
+        if (n_out) *n_out = (uint32_t)audio_front_n_out((int)nsamp);
+        return 0;
+    } catch (const std::exception& e) { return fail("wspr_audio_to_iq", e); }
+}
+
+void wspr_audio_constants(float* taps_i511, float* taps_q511, int* samples_per_output) {
+    float gi[AUDIO_FRONT_NTAPS], gq[AUDIO_FRONT_NTAPS];
+    wspr::audio_front_taps(gi, gq);
+    if (taps_i511) std::memcpy(taps_i511, gi, sizeof gi);
+    if (taps_q511) std::memcpy(taps_q511, gq, sizeof gq);
+    if (samples_per_output) *samples_per_output = AUDIO_FRONT_DECIM;
 }
 
 wspr_session* wspr_session_create(struct decoder_options options) {

@@ -193,7 +193,7 @@ size_t Context::release_buffers() {
                               &c.symbuf, &c.rmsbuf, &c.jobs, &c.subscratch, &c.nvalid, &c.decscratch, &c.tabs, &c.pw, &c.pwfreq, &c.lagprune,
                               &c.lists, &c.scrsync, &c.psavg, &c.densein, &c.fz_sym, &c.fz_off, &c.fz_ret, &c.fz_cyc, &c.fz_met, &c.fz_max,
                               &c.fz_dat, &c.fz_steps, &c.fz_pool, &c.streamraw, &c.streamstate, &c.synthtx, &c.synthoff, &c.synthfirst,
-                              &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out, &c.spr_tw, &c.spr_jobs, &c.spr_ckpt, &c.spr_out})
+                              &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out, &c.spr_tw, &c.spr_jobs, &c.spr_ckpt, &c.spr_out, &c.audiopcm})
                 freed += b->release();
             for (PinBuf* b : {&c.h_npk, &c.h_cand, &c.h_items, &c.h_sync, &c.h_sym, &c.h_rms, &c.h_jobs, &c.h_jobs2, &c.h_seglist,
                               &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_sprjobs, &c.h_sprout, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
@@ -652,6 +652,24 @@ int Context::decimate_device(const void* d_raw, size_t bytes_per_seg, int nseg, 
     }
     return 0;
 }
+
+// K12: the audio front end on the lane's stream, then (normalise) the receiver's scaling as for the RTL-SDR front end
+int Context::audio_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, float* dI, float* dQ, int normalise) {
+    Impl& c = *d;
+    if (nseg <= 0) return 0;
+    launch_audio_front(static_cast<const int16_t*>(d_pcm), pcm_stride, nsamp, nseg, dI, dQ, c.stream);
+    if (normalise) launch_normalise(dI, dQ, nullptr, nseg, kMaxSamples, c.stream);
+    HIP_OK(hipGetLastError());
+    if (c.blocking) {
+        HIP_OK(hipEventRecord(c.ev_sync, c.stream));
+        host_wait(c.ev_sync);
+    } else {
+        HIP_OK(hipStreamSynchronize(c.stream));
+    }
+    return 0;
+}
+
+int16_t* Context::audio_pcm(size_t nsamp) { return static_cast<int16_t*>(d->audiopcm.need(((nsamp + 7) & ~(size_t)7) * 2 + 16)); }
 
 // one chunk of one receiver's stream: state in, appended outputs and state out (host buffers)
 int Context::decimate_stream(DecimState* h_state, const uint8_t* iq, size_t nbytes, float* I, float* Q, uint32_t fill,

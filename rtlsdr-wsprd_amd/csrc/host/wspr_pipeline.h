@@ -242,6 +242,9 @@ public:
     // one chunk of EACH of n receivers' streams (all of nbytes): one transfer and one launch set for all of them
     int decimate_stream_many(DecimState* const* h_states, const uint8_t* const* iq, size_t nbytes, int n, float* const* I,
                              float* const* Q, const uint32_t* fill, uint32_t cap, uint32_t* new_fill);
+    // K12 (k12_audio.hip): nseg validated records of 16-bit audio resident on the device into IQ rows; complete on return
+    int audio_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, float* dI, float* dQ, int normalise);
+    int16_t* audio_pcm(size_t nsamp);   // device scratch for one record (wspr_audio_to_iq)
 
     // K8 (wspr_capi_synth.hip): a validated, sorted transmission list into nseg device rows; complete on return
     int synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, float sigma, uint64_t seed,

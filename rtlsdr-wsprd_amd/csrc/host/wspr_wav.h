@@ -1,0 +1,10 @@
+// RIFF/WAVE reader of wspr_read_wav_file() (include/wspr_mi355x.h).  Plain C++, no HIP: the file is untrusted input.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+
+namespace wspr {
+// PCM (format tag 1), 1 channel, 16 bit, 12 000 Hz only.  Returns the samples stored in pcm[0 .. cap), 0 on any error or any
+// other format.
+size_t read_wav_file(const char* filename, int16_t* pcm, size_t cap);
+}  // namespace wspr

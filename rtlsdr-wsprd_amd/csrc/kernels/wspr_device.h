@@ -248,5 +248,10 @@ void front_end_constants(float* taps33, int* samples_per_output);   // the FIR t
 // states: null = zero state, whole blocks only; else one DecimState per segment row, read and updated
 void launch_decimate(const uint8_t* raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ,
                      int* n_out, int32_t* scratch, hipStream_t st, DecimState* states = nullptr);
+// K12, the 12 kHz audio front end (k12_audio.hip; the definition in audio_front.h): nseg records of nsamp 16-bit samples
+// (row s at pcm + s * pcm_stride; pcm 16-byte aligned, pcm_stride a multiple of 8 and >= nsamp, 0 <= nsamp <= 1 440 000)
+// into rows of kIqStride floats, the whole row written (zero from min(ceil(nsamp / 32), 45000) on).
+void launch_audio_front(const int16_t* pcm, size_t pcm_stride, int nsamp, int nseg, float* dI, float* dQ, hipStream_t st);
+void audio_front_taps(float* gi511, float* gq511);                  // the two tap tables of audio_front.h as floats
 
 }  // namespace wspr
