@@ -73,6 +73,24 @@ int wspr_stage_fft_bank(const float *idat, const float *qdat, int nseg, int samp
 int wspr_stage_candidates(const float *idat, const float *qdat, int nseg, int samples,
                           size_t seg_stride, int coarse, int maxdrift, struct cand *cand_out,
                           int *npk_out, float *noise_out, float *smspec_out);
+/* The same two stages on a caller's spectrogram instead of a record: ps[s][bin 0..511][t 0..blocks) in the reference's
+ * layout, any blocks in 1..347 (blocks < 347: a short record).  Rows 48..464 go into the device layout (pitch 352); every
+ * float that layout does not define -- the five pitch columns, and the columns from `blocks` on -- is set to NaN, so a
+ * result that depends on one is not the oracle's.  Then the production launchers run (time average, peak picker, coarse
+ * sync when coarse != 0) and fetch_candidates(), and the outputs are those of wspr_stage_candidates().
+ *   active / nactive: NULL = every segment; else the segments to process, in this order (the launchers' device segment
+ *     list, as every pass after the first passes one).  A segment not listed keeps what the hook set before the
+ *     launches: npk 0 and NaN noise / smspec, or, with a caller's list, that list with shift, drift and sync zero.
+ *   cand_freq / cand_n: NULL = the picker runs; else cand_freq[s][200] (Hz as struct cand holds it; the first cand_n[s]
+ *     count, 0..200 each) replaces it: the picker is skipped, noise_out / smspec_out stay NaN, and snr is a placeholder
+ *     that falls with the index.  Each frequency must lie on the picker's bins (if0 = freq / (DF / 2) + 256 in 106..406).
+ *   k3_kernel: 0 = the product's choice (by batch size; WSPR_K3_KERNEL), 1 = one wave per frequency bin, 2 = one lane per
+ *     (candidate, lag) (full-length records only: a short record takes the wave kernel).
+ * Returns 0, or -1 for an argument out of range (nothing is launched). */
+int wspr_stage_candidates_ps(const float *ps, int nseg, int blocks, int coarse, int maxdrift,
+                             const int *active, int nactive, const float *cand_freq, const int *cand_n,
+                             int k3_kernel, struct cand *cand_out, int *npk_out, float *noise_out,
+                             float *smspec_out);
 
 /* Times `iters` passes of the FFT+sync stage (K1,K2,K3) on resident data with HIP events on the
  * launch stream, after one untimed pass.  ms must hold 8 doubles: ms[0] = K1 (sum over the segment chunks of a pass),

@@ -270,6 +270,21 @@ void coarse_sync_kernel(const float* __restrict__ ps, const int* __restrict__ se
 #pragma unroll
             for (int q = 0; q < 8; ++q) a[q] = A[q * kCsPitch + off];
         };
+        // Symbols 0..6, the only ones a negative time index can belong to.  In a record of fewer than ten blocks the
+        // reference's flat index then reaches further back than the previous bin's row (7 blocks, index -10: two rows
+        // back, column 4).  Those rows are not all staged: read the values where they lie (the lowest is bin
+        // if0 - 15 >= 91, inside the spectrogram).
+        auto load_head = [&](int k, float (&a)[8]) {
+            const int kidx = k0 + 2 * k;
+            if (!kFull && kidx < -blocks) {
+                const int back = (blocks - 1 - kidx) / blocks;
+                const float* __restrict__ g = (half ? src_b : src_a) + (fi + 1 - back) * kPsTPitch + (kidx + back * blocks);
+#pragma unroll
+                for (int q = 0; q < 8; ++q) a[q] = sqrtf(g[q * kPsTPitch]);
+                return;
+            }
+            load_any(k, a);
+        };
         // Even and odd symbols read through two base pointers the compiler cannot relate: otherwise it fuses the
         // loads of symbols k and k+1 (two dwords apart) into ds_read2_b32 pairs, whose halves then have to be
         // shuffled into the (lo, hi) operand pairs with a dozen moves per step.
@@ -298,12 +313,12 @@ void coarse_sync_kernel(const float* __restrict__ ps, const int* __restrict__ se
         };
         // symbols 0..80, the next symbol's amplitudes in flight while the current one is folded in
         float a0[8], a1[8];
-        load_any(0, a0);
+        load_head(0, a0);
 #pragma unroll
         for (int k = 0; k < 6; k += 2) {                         // 0..5: lags < 0 still reach before the record
-            load_any(k + 1, a1);
+            load_head(k + 1, a1);
             step1(k, a0);
-            load_any(k + 2, a0);
+            load_head(k + 2, a0);
             step1(k + 1, a1);
         }
         for (int k = 6; k < 80; k += 2) {
@@ -625,7 +640,7 @@ void launch_pick_peaks(const float* ps, const int* seg_list, int nseg_active, in
 
 void launch_coarse_sync(const float* ps, const int* seg_list, int nseg_active, int blocks,
                         DevCand* cand, const int* npk, int maxdrift,
-                        const DeviceTables& t, hipStream_t st) {
+                        const DeviceTables& t, hipStream_t st, int kernel) {
     if (nseg_active <= 0) return;
     static const SyncBits bits = [] {
         SyncBits b{};
@@ -638,7 +653,8 @@ void launch_coarse_sync(const float* ps, const int* seg_list, int nseg_active, i
     // pay two staging round trips each, which a launch of a few hundred candidate pairs cannot hide (1 024
     // single-signal segments: 59 vs 46 us; 8 192 x 10 signals: 0.93 vs 1.15 ms).  WSPR_K3_KERNEL=waves / lane force one.
     static const int forced = [] { const char* e = lab_env("WSPR_K3_KERNEL"); return !e ? 0 : (e[0] == 'w' ? 1 : 2); }();
-    const bool lane_kernel = forced ? forced == 2 : nseg_active >= 1536;
+    const int chosen = kernel ? kernel : forced;             // a caller's choice comes before the environment's
+    const bool lane_kernel = chosen ? chosen == 2 : nseg_active >= 1536;
     if (blocks == kMaxBlocks && lane_kernel)
         hipLaunchKernelGGL(coarse_sync_lane_kernel, dim3(nseg_active, gy), dim3(64), 0, st, ps, seg_list, cand, npk,
                            maxdrift, bits);

@@ -119,9 +119,11 @@ void launch_time_average(const float* ps, const int* seg_list, int nseg_active, 
 void launch_pick_peaks(const float* ps, const int* seg_list, int nseg_active, int blocks, float* psavg,
                        DevCand* cand, int* npk, float* noise_out, float* smspec_out,
                        const DeviceTables& t, hipStream_t st, bool have_avg = false);
+// kernel: 0 = the launcher's own choice (by batch size; WSPR_K3_KERNEL in the lab build), 1 = one wave per frequency bin,
+// 2 = one lane per (candidate, lag) where the record is full length (a stage hook of the lab build passes 1 or 2)
 void launch_coarse_sync(const float* ps, const int* seg_list, int nseg_active, int blocks,
                         DevCand* cand, const int* npk, int maxdrift,
-                        const DeviceTables& t, hipStream_t st);
+                        const DeviceTables& t, hipStream_t st, int kernel = 0);
 // nhyp hypotheses per item, results in sync_out[item][nhyp]:
 // mode 0: lags shift_coarse-128 + lagstep*h at freq_coarse
 // mode 1: frequencies state.freq + (ifmin+h)*fstep at state.shift

@@ -45,7 +45,8 @@ def test_lab_library_is_the_product_plus_the_bench_header():
     header's functions is in the product."""
     funcs, data = declared_symbols()
     bfuncs, bdata = declared_symbols("wspr_mi355x_bench.h")
-    assert {"wspr_decode_batch_trace", "wspr_stage_fft_bank", "wspr_stage_candidates", "wspr_bench_fft_sync", "wspr_bench_valu",
+    assert {"wspr_decode_batch_trace", "wspr_stage_fft_bank", "wspr_stage_candidates", "wspr_stage_candidates_ps", "wspr_bench_fft_sync",
+            "wspr_bench_valu",
             "wspr_bench_decimate", "wspr_calib_read", "wspr_calib_copy", "wspr_calib_copy16", "wspr_calib_valu",
             "wspr_set_front_end_cus"} == bfuncs and not bdata
     out = subprocess.run(["nm", "-D", "--defined-only", w.LAB_PATH], capture_output=True, text=True, check=True).stdout

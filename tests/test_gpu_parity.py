@@ -173,6 +173,55 @@ def test_coarse_sync_of_a_large_batch_matches_oracle(w, synth_batch, ref_iq, max
                 assert (g.freq, g.shift, g.drift, g.sync, g.snr) == (o.freq, o.shift, o.drift, o.sync, o.snr), (s, j)
 
 
+def band_edge_records():
+    """Two records with tones on the picker's last bins inside +-110 Hz (smoothed bins 55 and 355, +-109.86 Hz): their
+    candidates have if0 106 and 406, so the coarse sync stages rows 100 .. 110 and 400 .. 410 -- the first and the last
+    row the fused K1 stores."""
+    rng = np.random.default_rng(55355)
+    t = np.arange(NS) / 375.0
+    recs = []
+    for a_lo, a_hi in ((0.3, 0.2), (0.1, 0.25)):
+        z = 0.02 * (rng.normal(size=NS) + 1j * rng.normal(size=NS))
+        z = z + a_lo * np.exp(-2j * np.pi * 150 * (375.0 / 512.0) * t) + a_hi * np.exp(2j * np.pi * 150 * (375.0 / 512.0) * t)
+        recs.append(z)
+    return (np.stack([z.real for z in recs]).astype(np.float32), np.stack([z.imag for z in recs]).astype(np.float32))
+
+
+def test_band_edge_candidates_through_the_fused_fft_bank(w, synth_batch, ref_iq):
+    """256 segments (the fused K1, which stores rows 100 .. 410 only): candidates on both edge bins read exactly up to
+    the first and the last stored row.  A call on the batch scaled by 10^3 comes first, so that whatever the fused K1
+    does not store holds foreign values."""
+    eI, eQ = band_edge_records()
+    I0 = np.concatenate([ref_iq[0][None], synth_batch[0], eI])
+    Q0 = np.concatenate([ref_iq[1][None], synth_batch[1], eQ])
+    n0 = I0.shape[0]
+    reps = -(-256 // n0)
+    I = np.tile(I0, (reps, 1))[:256].copy(); Q = np.tile(Q0, (reps, 1))[:256].copy()
+    nseg = 256
+    cands = (w.cand * (200 * nseg))()
+    npk = (C.c_int * nseg)()
+    noise = np.zeros(nseg, np.float32)
+    sm = np.zeros((nseg, 411), np.float32)
+    Ik, Qk = I * np.float32(1e3), Q * np.float32(1e3)
+    assert w.lab().wspr_stage_candidates(ol.ptr(Ik), ol.ptr(Qk), nseg, NS, NS, 1, 4, C.addressof(cands), C.addressof(npk),
+                                         None, None) == 0
+    assert w.lab().wspr_stage_candidates(ol.ptr(I), ol.ptr(Q), nseg, NS, NS, 1, 4, C.addressof(cands), C.addressof(npk),
+                                         ol.ptr(noise), ol.ptr(sm)) == 0
+    L = ol.lib()
+    if0_seen = set()
+    for s0 in range(n0):
+        onpk, oc, onoise, osm = _oracle_cands(I0[s0], Q0[s0], 0)
+        if0_seen |= {int(oc[j].freq / (375.0 / 256.0 / 2.0) + 256.0) for j in range(onpk)}
+        L.orc_coarse_sync(ol.ptr(oracle_ps(I0[s0], Q0[s0])), C.c_int(347), oc, C.c_int(onpk), C.c_int(4))
+        for s in range(s0, nseg, n0):
+            assert npk[s] == onpk
+            assert noise[s] == np.float32(onoise) and np.array_equal(sm[s], osm), s
+            for j in range(onpk):
+                g, o = cands[200 * s + j], oc[j]
+                assert (g.freq, g.shift, g.drift, g.sync, g.snr) == (o.freq, o.shift, o.drift, o.sync, o.snr), (s, j)
+    assert {106, 406} <= if0_seen
+
+
 @pytest.mark.parametrize("samples", [40000, 44992, 2048, 1024])
 def test_short_records_through_the_fused_fft_bank(w, synth_batch, ref_iq, samples):
     """Records shorter than 45 000 samples in a batch large enough for the fused K1 (>= 256 segments): the last group
@@ -213,6 +262,30 @@ def test_short_records_through_the_fused_fft_bank(w, synth_batch, ref_iq, sample
             assert noise[s] == np.float32(onoise.value) and np.array_equal(sm[s], osm), (s, samples)
             for j in range(onpk):
                 assert (cands[200 * s + j].freq, cands[200 * s + j].snr) == (oc[j].freq, oc[j].snr), (s, j)
+    if samples > 2048:
+        return
+    # and through coarse_sync_kernel<false> (symbols behind the record masked; 1 024 samples are 7 blocks: a negative
+    # time index reaches two rows back)
+    rc = w.lab().wspr_stage_candidates(ol.ptr(I), ol.ptr(Q), nseg, samples, samples, 1, 4, C.addressof(cands),
+                                       C.addressof(npk), ol.ptr(noise), ol.ptr(sm))
+    assert rc == 0
+    for s0 in range(n0):
+        ps = np.zeros((512, blocks), np.float32)
+        Iz = np.concatenate([I0[s0], np.zeros(NS - samples, np.float32)])
+        Qz = np.concatenate([Q0[s0], np.zeros(NS - samples, np.float32)])
+        L.orc_fft_bank(ol.ptr(Iz), ol.ptr(Qz), C.c_int(samples), ol.ptr(ps))
+        oc = (ol.Cand * 200)()
+        onoise = C.c_float()
+        osm = np.zeros(411, np.float32)
+        onpk = L.orc_pick_peaks(ol.ptr(ps), C.c_int(blocks), oc, C.byref(onoise), ol.ptr(osm), None)
+        L.orc_coarse_sync(ol.ptr(ps), C.c_int(blocks), oc, C.c_int(onpk), C.c_int(4))
+        for rep in range(reps):
+            s = rep * n0 + s0
+            assert npk[s] == onpk, (s, samples)
+            assert noise[s] == np.float32(onoise.value) and np.array_equal(sm[s], osm), (s, samples)
+            for j in range(onpk):
+                g, o = cands[200 * s + j], oc[j]
+                assert (g.freq, g.shift, g.drift, g.sync, g.snr) == (o.freq, o.shift, o.drift, o.sync, o.snr), (s, j, samples)
 
 
 # ------------------------------------------------------------------ K4 / K5
