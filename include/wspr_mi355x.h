@@ -305,6 +305,58 @@ int wspr_synth(const wspr_synth_tx *tx, int ntx, float noise_sigma, uint64_t see
  * (negative: no usable device) and hands back the first spot (first may be NULL). */
 int wspr_selftest(struct decoder_options options, struct decoder_results *first);
 
+/* ---- fading channel of the synthesiser (K13) ----------------------------------------------------------------
+ * Opt-in: wspr_synth_batch_device() / wspr_synth() with an HF channel per transmission, under the same contract (a CPU
+ * reproduces every sample; tests/helpers/fade_check.cpp is the serial form, rtlsdr-wsprd_amd/csrc/kernels/fade.h the
+ * shared arithmetic).  A channel is up to two paths, each with a linear gain, a Doppler shift (Hz) and a Doppler spread
+ * sigma (Hz).  NO PATH DELAY IS MODELLED: differential delays on HF are 0.5 - 2 ms, so the coherence bandwidth is
+ * hundreds of Hz against a 6 Hz signal; a delay is then a constant phase, which the random gain absorbs.
+ *
+ * The draws of a transmission are identified by S = seg_index0 + seg (the global segment), q = its ordinal among that
+ * segment's transmissions in list order (0-based), the path p and its own sample index n = 0 .. 41 471 -- so a
+ * realisation does not depend on how a job is split into calls, batches or ranks.
+ *
+ * A path is one of three kinds:
+ *   skipped   gain == 0: it adds nothing.
+ *   specular  sigma == 0: G_p[n] = (gain, 0).
+ *   diffuse   sigma > 0.  All in double, unfused, in this order:
+ *               s    = 375.0 / ((2.0*1.4142135623730951*3.14159265358979323846) * (double)sigma)
+ *                      -- the Gaussian pulse's standard deviation in samples;
+ *               L    = (int)s -- the spacing of the white impulses (sigma <= 10 gives L >= 4 and 1 <= s/L < 1.25);
+ *               beta = 1.0/(2.0*s*s);     c = (double)gain / sqrt(2.0*(s*1.7724538509055159)/(double)L);
+ *               W[k] = a complex float32 draw of unit variance per rail: Philox-4x32-10 keyed by the seed, counter =
+ *                      (k + 16, 1 + 2q + p, S low, S high) -- the noise uses counter word 1 = 0, so the two never
+ *                      collide -- through exactly the Box-Muller of the noise at sigma 1;
+ *               with kc = n / L:  sum = 0.0;  for k = kc-7 .. kc+8 in rising k, d = n - k*L (int):
+ *                      sum += (double)W[k] * exp(-((double)d*(double)d)*beta), each rail separately;  G_p[n] = c * sum.
+ *             Sixteen terms: the nearest dropped impulse is at least 5.6 s away (weight below 2e-7), and the spectral
+ *             images of the impulse train lie below exp(-2 pi^2) = 3e-9 in amplitude.  exp is synth_exp() of
+ *             synth_math.h: reduction by ln 2 in two pieces, the Taylor polynomial to degree 12, 2^k through the exponent
+ *             bits; a fixed sequence of IEEE double operations on [-40, 0] (here the argument is >= -32), within 2^-40
+ *             of exp (measured: profiles/fade_channel.json), no maths library.
+ *   shift     either kind: if shift != 0, G_p[n] is rotated by the synthesiser's (ss, cc) = sincos(w*(double)n), w =
+ *             2.0*3.14159265358979323846*(1/375.0)*(double)shift:  (re*cc - im*ss, re*ss + im*cc).
+ * G[n] = (0.0, 0.0), then + G_0[n], then + G_1[n] (skipped paths left out).  With (sn, cs) the synthesiser's sine and cosine
+ * of phi, step 3 of the synthesiser's contract above becomes
+ *   x_I = (float)((double)x_I + amp*(cs*G.re - sn*G.im));     x_Q = (float)((double)x_Q + amp*(sn*G.re + cs*G.im)).
+ * Steps 1 and 2, the list order, the phase recurrence and the index rule are unchanged.  The channel {(1,0,0),(0,0,0)}
+ * gives the unfaded samples bit for bit.
+ * A diffuse path's Doppler spectrum is Gaussian with standard deviation sigma (its 2 sigma is what Watterson-model
+ * tables call the Doppler spread) and E|G_p|^2 = gain^2: one diffuse path is Rayleigh fading, a specular plus a diffuse
+ * one Rician. */
+typedef struct wspr_synth_path    { float gain, shift, sigma; } wspr_synth_path;      /* linear, Hz, Hz */
+typedef struct wspr_synth_channel { wspr_synth_path path[2]; } wspr_synth_channel;    /* 24 bytes, one per transmission */
+/* wspr_synth_batch_device() with ch[t] the channel of tx[t]; ch == NULL is the unfaded call.  Flags, rows, stream contract,
+ * lane turn and scratch ownership (64 B more per transmission) are those of wspr_synth_batch_device().  Returns 0; -1
+ * with a line on stderr and NOTHING WRITTEN for everything that call refuses and for a non-finite gain, shift or sigma,
+ * a sigma that is neither 0 nor within 0.001 .. 10 Hz, or |shift| > 100 Hz. */
+int wspr_synth_faded_batch_device(const wspr_synth_tx *tx, const wspr_synth_channel *ch, int ntx, int nseg,
+                                  int seg_index0, float noise_sigma, uint64_t seed, int flags,
+                                  void *d_idat, void *d_qdat);
+/* One segment into host rows of 45000 floats, seg_index0 = 0: row 0 of the batch call (as wspr_synth()). */
+int wspr_synth_faded(const wspr_synth_tx *tx, const wspr_synth_channel *ch, int ntx, float noise_sigma,
+                     uint64_t seed, int flags, float *I, float *Q);
+
 /* ---- receiver session --------------------------------------------------------------------
  * The reference's rx_state (two I/Q buffers of 45000 samples, their fill counters, the active index,
  * rtlsdr_wsprd.c:78-90), the decimator's static state (:135-160) and the body of its decoder thread (:263-328) as

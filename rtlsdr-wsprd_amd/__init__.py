@@ -54,6 +54,18 @@ class wspr_synth_tx(C.Structure):            # include/wspr_mi355x.h: one transm
 SYNTH_TX_DTYPE = np.dtype([("seg", "<i4"), ("f0", "<f4"), ("t0", "<f4"), ("amp", "<f4"), ("drift", "<f4"),
                            ("symbols", "u1", (162,)), ("pad", "u1", (2,))])
 assert SYNTH_TX_DTYPE.itemsize == C.sizeof(wspr_synth_tx) == 184
+
+
+class wspr_synth_path(C.Structure):          # one path of a fading channel: linear gain, Doppler shift and spread in Hz
+    _fields_ = [("gain", C.c_float), ("shift", C.c_float), ("sigma", C.c_float)]
+
+
+class wspr_synth_channel(C.Structure):       # the channel of one transmission (wspr_synth_faded*()), 24 bytes
+    _fields_ = [("path", wspr_synth_path * 2)]
+
+
+SYNTH_CHANNEL_DTYPE = np.dtype([("path", [("gain", "<f4"), ("shift", "<f4"), ("sigma", "<f4")], (2,))])
+assert SYNTH_CHANNEL_DTYPE.itemsize == C.sizeof(wspr_synth_channel) == 24
 SYNTH_ACCUMULATE = 1
 SYNTH_NORMALISE = 2
 
@@ -142,6 +154,11 @@ def _bind(path):
     L.wspr_synth_batch_device.restype = C.c_int
     L.wspr_synth.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
     L.wspr_synth.restype = C.c_int
+    L.wspr_synth_faded_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64,
+                                                C.c_int, C.c_void_p, C.c_void_p]
+    L.wspr_synth_faded_batch_device.restype = C.c_int
+    L.wspr_synth_faded.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+    L.wspr_synth_faded.restype = C.c_int
     L.wspr_audio_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
     L.wspr_audio_batch_device.restype = C.c_int
     L.wspr_audio_to_iq.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
@@ -352,6 +369,56 @@ def wspr_synth(items, noise_sigma=0.0, seed=0, flags=0, I=None, Q=None):
     arr = synth_tx_list(items)
     if lib().wspr_synth(C.addressof(arr), len(items), noise_sigma, seed, flags, _ptr(I), _ptr(Q)) != 0:
         raise RuntimeError("wspr_synth failed (bad arguments, or no usable HIP device)")
+    return I, Q
+
+
+def synth_channel_list(channels):
+    """[[(gain, shift, sigma), (gain, shift, sigma)], ...], one per transmission -> ctypes array of wspr_synth_channel."""
+    arr = (wspr_synth_channel * max(1, len(channels)))()
+    for k, ch in enumerate(channels):
+        if len(ch) != 2:
+            raise ValueError("a channel is two paths (gain, shift, sigma); a path with gain 0 is skipped")
+        for p in range(2):
+            arr[k].path[p].gain, arr[k].path[p].shift, arr[k].path[p].sigma = ch[p]
+    return arr
+
+
+def _synth_channels(channels, n):
+    """(pointer or None, keep-alive) for the channels of n transmissions: None, a list, or a SYNTH_CHANNEL_DTYPE array."""
+    if channels is None:
+        return None, None
+    if isinstance(channels, np.ndarray):
+        assert channels.dtype == SYNTH_CHANNEL_DTYPE and channels.flags.c_contiguous and channels.size == n
+        return channels.ctypes.data, channels
+    if len(channels) != n:
+        raise ValueError("one channel per transmission")
+    arr = synth_channel_list(channels)
+    return C.addressof(arr), arr
+
+
+def wspr_synth_faded_batch_device(items, channels, nseg, d_i, d_q, seg_index0=0, noise_sigma=0.0, seed=0, flags=0):
+    """wspr_synth_faded_batch_device(): wspr_synth_batch_device() with an HF fading channel per transmission (K13).
+    channels: one [(gain, shift, sigma), (gain, shift, sigma)] per transmission (or a numpy array of SYNTH_CHANNEL_DTYPE);
+    None is the unfaded call.  Returns the library's code (0, or -1 with nothing written)."""
+    if isinstance(items, np.ndarray):
+        assert items.dtype == SYNTH_TX_DTYPE and items.flags.c_contiguous
+        tx, n = items.ctypes.data, int(items.size)
+    else:
+        arr = synth_tx_list(items)
+        tx, n = C.addressof(arr), len(items)
+    ch, _keep = _synth_channels(channels, n)
+    return lib().wspr_synth_faded_batch_device(tx, ch, n, nseg, seg_index0, noise_sigma, seed, flags, d_i, d_q)
+
+
+def wspr_synth_faded(items, channels, noise_sigma=0.0, seed=0, flags=0, I=None, Q=None):
+    """wspr_synth_faded(): one faded segment into host rows of 45000 floats (given rows are copied and matter with
+    SYNTH_ACCUMULATE).  Returns (I, Q); raises if the library refuses the call."""
+    I = np.zeros(NSAMPLES, np.float32) if I is None else np.array(I, np.float32).copy()
+    Q = np.zeros(NSAMPLES, np.float32) if Q is None else np.array(Q, np.float32).copy()
+    arr = synth_tx_list(items)
+    ch, _keep = _synth_channels(channels, len(items))
+    if lib().wspr_synth_faded(C.addressof(arr), ch, len(items), noise_sigma, seed, flags, _ptr(I), _ptr(Q)) != 0:
+        raise RuntimeError("wspr_synth_faded failed (bad arguments, or no usable HIP device)")
     return I, Q
 
 

@@ -1,5 +1,6 @@
 // C ABI of libwspr_mi355x.so (declared in include/wspr_mi355x.h): the signal synthesiser -- wspr_synth_batch_device(),
-// wspr_synth() and wspr_selftest(), the reference's decoderSelfTest() (rtlsdr_wsprd.c:729-789) on the device.
+// wspr_synth() and wspr_selftest(), the reference's decoderSelfTest() (rtlsdr_wsprd.c:729-789) on the device -- and the
+// same two calls with an HF fading channel per transmission, wspr_synth_faded_batch_device() and wspr_synth_faded().
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
@@ -9,18 +10,19 @@
 
 #include "wspr_capi_impl.h"
 #include "wspr_context_impl.h"
-#include "../kernels/synth_math.h"
+#include "../kernels/fade.h"
 
 using wspr::Context;
 using namespace wspr::capi;
 
+static_assert(sizeof(wspr_synth_channel) == 24 && sizeof(wspr_synth_path) == 12, "public channel layout");
 static_assert(sizeof(wspr_synth_tx) == 184 && sizeof(wspr_synth_tx) == sizeof(wspr::SynthTx),
               "public and device transmission layouts differ");
 
 namespace wspr {
 
 int Context::synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, float sigma, uint64_t seed,
-                          int flags, float* dI, float* dQ) {
+                          int flags, float* dI, float* dQ, const FadeChannel* fade) {
     Impl& c = *d;
     if (nseg <= 0) return 0;
     const hipStream_t st = c.stream;
@@ -38,8 +40,18 @@ int Context::synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long 
         d_ckpt = static_cast<double*>(c.synthckpt.need(synth_checkpoint_doubles(ntx) * sizeof(double)));
         upload(d_tx, tx, (size_t)ntx * sizeof(SynthTx), st);
     }
-    launch_synth(d_tx, ntx, d_off, nseg, seg_index0, sigma, (unsigned long long)seed, (flags & kSynthFlagAccumulate) != 0,
-                 d_ckpt, d_first, dI, dQ, st);
+    if (fade) {
+        FadeChannel* d_fade = nullptr;
+        if (ntx > 0) {
+            d_fade = static_cast<FadeChannel*>(c.synthfade.need((size_t)ntx * sizeof(FadeChannel)));
+            upload(d_fade, fade, (size_t)ntx * sizeof(FadeChannel), st);
+        }
+        launch_synth_faded(d_tx, d_fade, ntx, d_off, nseg, seg_index0, sigma, (unsigned long long)seed,
+                           (flags & kSynthFlagAccumulate) != 0, d_ckpt, d_first, dI, dQ, st);
+    } else {
+        launch_synth(d_tx, ntx, d_off, nseg, seg_index0, sigma, (unsigned long long)seed, (flags & kSynthFlagAccumulate) != 0,
+                     d_ckpt, d_first, dI, dQ, st);
+    }
     if (flags & kSynthFlagNormalise) launch_normalise(dI, dQ, nullptr, nseg, kMaxSamples, st);   // rtlsdr_wsprd.c:290-305
     HIP_OK(hipGetLastError());
     if (c.blocking) {                                          // off / tx are host memory of this call: wait either way
@@ -79,6 +91,22 @@ bool synth_args_ok(const char* where, const wspr_synth_tx* tx, int ntx, int nseg
     if (why) { fprintf(stderr, "libwspr_mi355x: %s: %s\n", where, why); return false; }
     return true;
 }
+// The channels of a faded call, likewise; fills `out` with the constants the kernel takes (fade.h).
+bool fade_args_ok(const char* where, const wspr_synth_channel* ch, int ntx, std::vector<wspr::FadeChannel>& out) {
+    out.resize((size_t)ntx);
+    for (int t = 0; t < ntx; ++t)
+        for (int p = 0; p < 2; ++p) {
+            const wspr_synth_path& a = ch[t].path[p];
+            const char* why = nullptr;
+            if (!std::isfinite(a.gain) || !std::isfinite(a.shift) || !std::isfinite(a.sigma)) why = "gain, shift or sigma is not finite";
+            else if (a.sigma != 0.0f && !(a.sigma >= wspr::kFadeMinSigma && a.sigma <= wspr::kFadeMaxSigma))
+                why = "sigma neither 0 nor within 0.001 .. 10 Hz";
+            else if (std::fabs(a.shift) > wspr::kFadeMaxShift) why = "|shift| above 100 Hz";
+            if (why) { fprintf(stderr, "libwspr_mi355x: %s: transmission %d, path %d: %s\n", where, t, p, why); return false; }
+            out[(size_t)t].path[p] = wspr::fade_path_setup(a.gain, a.shift, a.sigma);
+        }
+    return true;
+}
 }  // namespace
 
 extern "C" {
@@ -96,11 +124,30 @@ int wspr_synth_batch_device(const wspr_synth_tx* tx, int ntx, int nseg, int seg_
     } catch (const std::exception& e) { return fail("wspr_synth_batch_device", e); }
 }
 
-int wspr_synth(const wspr_synth_tx* tx, int ntx, float noise_sigma, uint64_t seed, int flags, float* I, float* Q) {
+int wspr_synth_faded_batch_device(const wspr_synth_tx* tx, const wspr_synth_channel* ch, int ntx, int nseg, int seg_index0,
+                                  float noise_sigma, uint64_t seed, int flags, void* d_idat, void* d_qdat) {
     LaneTurn lane_turn;
     try {
-        if (!synth_args_ok("wspr_synth", tx, ntx, 1, noise_sigma, flags)) return -1;
-        if (!I || !Q) { fprintf(stderr, "libwspr_mi355x: wspr_synth: no output rows\n"); return -1; }
+        std::vector<wspr::FadeChannel> fade;
+        if (!synth_args_ok("wspr_synth_faded_batch_device", tx, ntx, nseg, noise_sigma, flags)) return -1;
+        if (ch && !fade_args_ok("wspr_synth_faded_batch_device", ch, ntx, fade)) return -1;
+        if (nseg > 0 && (!d_idat || !d_qdat || ((reinterpret_cast<uintptr_t>(d_idat) | reinterpret_cast<uintptr_t>(d_qdat)) & 15))) {
+            fprintf(stderr, "libwspr_mi355x: wspr_synth_faded_batch_device: d_idat and d_qdat must be 16-byte aligned device rows\n");
+            return -1;
+        }
+        return Context::get().synth_device(tx, ntx, nseg, seg_index0, noise_sigma, seed, flags, (float*)d_idat, (float*)d_qdat,
+                                           ch ? fade.data() : nullptr);
+    } catch (const std::exception& e) { return fail("wspr_synth_faded_batch_device", e); }
+}
+
+// wspr_synth() and wspr_synth_faded(): one segment through the context's working rows
+static int synth_host(const char* where, const wspr_synth_tx* tx, const wspr_synth_channel* ch, int ntx, float noise_sigma,
+                      uint64_t seed, int flags, float* I, float* Q) {
+    try {
+        std::vector<wspr::FadeChannel> fade;
+        if (!synth_args_ok(where, tx, ntx, 1, noise_sigma, flags)) return -1;
+        if (ch && !fade_args_ok(where, ch, ntx, fade)) return -1;
+        if (!I || !Q) { fprintf(stderr, "libwspr_mi355x: %s: no output rows\n", where); return -1; }
         Context& c = Context::get();
         float* wi = c.work_i(1);
         float* wq = c.work_q(1);
@@ -109,7 +156,7 @@ int wspr_synth(const wspr_synth_tx* tx, int ntx, float noise_sigma, uint64_t see
             HIP_TRY(hipMemcpy(wi, I, bytes, hipMemcpyHostToDevice));
             HIP_TRY(hipMemcpy(wq, Q, bytes, hipMemcpyHostToDevice));
         }
-        const int rc = c.synth_device(tx, ntx, 1, 0, noise_sigma, seed, flags, wi, wq);
+        const int rc = c.synth_device(tx, ntx, 1, 0, noise_sigma, seed, flags, wi, wq, ch ? fade.data() : nullptr);
         if (rc) return rc;
         std::vector<float> oi(wspr::kMaxSamples), oq(wspr::kMaxSamples);    // both rails arrive before either is handed over
         HIP_TRY(hipMemcpy(oi.data(), wi, bytes, hipMemcpyDeviceToHost));
@@ -117,7 +164,18 @@ int wspr_synth(const wspr_synth_tx* tx, int ntx, float noise_sigma, uint64_t see
         std::memcpy(I, oi.data(), bytes);
         std::memcpy(Q, oq.data(), bytes);
         return 0;
-    } catch (const std::exception& e) { return fail("wspr_synth", e); }
+    } catch (const std::exception& e) { return fail(where, e); }
+}
+
+int wspr_synth(const wspr_synth_tx* tx, int ntx, float noise_sigma, uint64_t seed, int flags, float* I, float* Q) {
+    LaneTurn lane_turn;
+    return synth_host("wspr_synth", tx, nullptr, ntx, noise_sigma, seed, flags, I, Q);
+}
+
+int wspr_synth_faded(const wspr_synth_tx* tx, const wspr_synth_channel* ch, int ntx, float noise_sigma, uint64_t seed, int flags,
+                     float* I, float* Q) {
+    LaneTurn lane_turn;
+    return synth_host("wspr_synth_faded", tx, ch, ntx, noise_sigma, seed, flags, I, Q);
 }
 
 // decoderSelfTest(), rtlsdr_wsprd.c:729-789: "K1JT FN20QI 20" at 50 Hz, 2.0 s, amplitude 1 over noise of 0.02,

@@ -247,8 +247,9 @@ public:
     int16_t* audio_pcm(size_t nsamp);   // device scratch for one record (wspr_audio_to_iq)
 
     // K8 (wspr_capi_synth.hip): a validated, sorted transmission list into nseg device rows; complete on return
+    // fade: one FadeChannel (kernels/fade.h) per transmission in host memory for the fading channel (K13), or null (K8)
     int synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, float sigma, uint64_t seed,
-                     int flags, float* dI, float* dQ);
+                     int flags, float* dI, float* dQ, const FadeChannel* fade = nullptr);
     float* synth_rows();            // two rows of kIqStride floats of the context's own (wspr_selftest)
 
     struct Impl;

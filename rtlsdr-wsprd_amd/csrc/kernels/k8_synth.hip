@@ -26,7 +26,7 @@ namespace wspr {
 static_assert(kSynthSamples == kMaxSamples && kSynthSigLen == kSigLen, "synth_math.h and wspr_device.h disagree");
 
 namespace {
-constexpr int kCkptEvery = 64;
+constexpr int kCkptEvery = kSynthCkptEvery;               // 64
 constexpr int kCkptPerTx = kSigLen / kCkptEvery;          // 648
 constexpr int kPerThread = 16;
 constexpr int kTile = 256 * kPerThread;                   // 4 096 samples; 11 tiles cover a row of kIqStride floats
@@ -112,12 +112,17 @@ void synth_fill_kernel(const SynthTx* __restrict__ tx, int ntx, const int* __res
 
 size_t synth_checkpoint_doubles(int ntx) { return (size_t)kCkptPerTx * (size_t)(ntx > 0 ? ntx : 0); }
 
+// the phase checkpoints [checkpoint][transmission] and first indices alone: K13 (k13_fade.hip) fills from the same ones
+void launch_synth_phase(const SynthTx* tx, int ntx, double* ckpt, int* first, hipStream_t st) {
+    if (ntx > 0)
+        hipLaunchKernelGGL(synth_phase_kernel, dim3((ntx + 63) / 64), dim3(64), 0, st, tx, ntx, ckpt, first);
+}
+
 void launch_synth(const SynthTx* tx, int ntx, const int* seg_off, int nseg, long long seg_index0, float sigma,
                   unsigned long long seed, int accumulate, double* ckpt, int* first, float* dI, float* dQ,
                   hipStream_t st) {
     if (nseg <= 0) return;
-    if (ntx > 0)
-        hipLaunchKernelGGL(synth_phase_kernel, dim3((ntx + 63) / 64), dim3(64), 0, st, tx, ntx, ckpt, first);
+    launch_synth_phase(tx, ntx, ckpt, first, st);
     for (int s0 = 0; s0 < nseg; s0 += 32768)               // grid.y is limited to 65 535
         hipLaunchKernelGGL(synth_fill_kernel, dim3(kIqStride / kTile, nseg - s0 < 32768 ? nseg - s0 : 32768), dim3(256), 0, st,
                            tx, ntx, seg_off, first, ckpt, seg_index0, sigma, seed, accumulate, s0, dI, dQ);

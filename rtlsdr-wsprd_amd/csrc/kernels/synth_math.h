@@ -14,7 +14,9 @@
 //   synth_noise()   one complex float32 Gaussian draw as a pure function of (seed, segment, sample): Philox-4x32-10
 //                   (Salmon et al., SC'11) keyed by the seed, counter = (sample, 0, segment low, segment high), and the
 //                   Box-Muller transform with the logarithm as an atanh series in double and the angle through
-//                   glibc_sincosf.h.
+//                   glibc_sincosf.h.  synth_gauss() is the same draw for any first two counter words.
+//   synth_exp()     double exponential on [-40, 0] (the fading channel's Gaussian pulse, fade.h): reduction by ln 2 in
+//                   two pieces, the Taylor polynomial to degree 12, 2^k through the exponent bits.
 //   synth_dphi()    phase increment of symbol i, the reference's statement rtlsdr_wsprd.c:753 plus the decoder's drift
 //                   model (wsprd.c:156, 343).
 #pragma once
@@ -137,10 +139,12 @@ WSPR_HD double synth_log(double u) {
     const double p = 1.0 / 3.0 + z * (1.0 / 5.0 + z * (1.0 / 7.0 + z * (1.0 / 9.0 + z * (1.0 / 11.0 + z * (1.0 / 13.0 + z * (1.0 / 15.0))))));
     return (double)e * ln2 + (2.0 * s + 2.0 * s * z * p);
 }
-// One complex draw for (seed, global segment, sample): nI, nQ are float32 N(0, sigma^2), independent.
-WSPR_HD void synth_noise(uint64_t seed, int64_t segment, int sample, float sigma, float* nI, float* nQ) {
+// One complex float32 Gaussian draw for the Philox counter (c0, c1, segment low, segment high) under the seed's key:
+// nI, nQ are N(0, sigma^2), independent.  Counter word 1 names the stream: 0 is the noise (synth_noise()), 1 + 2q + p the
+// white impulses of path p of a segment's q-th transmission (fade.h).
+WSPR_HD void synth_gauss(uint64_t seed, int64_t segment, uint32_t c0, uint32_t c1, float sigma, float* nI, float* nQ) {
     uint32_t r[4];
-    synth_philox((uint32_t)sample, 0u, (uint32_t)(uint64_t)segment, (uint32_t)((uint64_t)segment >> 32),
+    synth_philox(c0, c1, (uint32_t)(uint64_t)segment, (uint32_t)((uint64_t)segment >> 32),
                  (uint32_t)seed, (uint32_t)(seed >> 32), r);
     // u in (0, 1] from 64 bits, theta in (0, 2 pi) from 32
     const double u = (((double)r[0] * 4294967296.0 + (double)r[1]) + 1.0) * 5.42101086242752217004e-20;   // 2^-64
@@ -151,6 +155,40 @@ WSPR_HD void synth_noise(uint64_t seed, int64_t segment, int sample, float sigma
     const float radf = (float)rad;
     *nI = (radf * cs) * sigma;
     *nQ = (radf * sn) * sigma;
+}
+// One complex draw for (seed, global segment, sample): nI, nQ are float32 N(0, sigma^2), independent.
+WSPR_HD void synth_noise(uint64_t seed, int64_t segment, int sample, float sigma, float* nI, float* nQ) {
+    synth_gauss(seed, segment, (uint32_t)sample, 0u, sigma, nI, nQ);
+}
+
+// ---- exponential ----------------------------------------------------------------------------------------------------
+// exp(x) for -40 <= x <= 0 (the Gaussian pulse of the fading channel, fade.h): x = k ln 2 + r with k = x / ln 2 rounded
+// to an integer and ln 2 in two pieces (the first has 32 bits, so k * ln2_hi is exact for |k| <= 58), |r| <= 0.3466;
+// exp(r) as its Taylor polynomial to r^12 by Horner's rule (the first term left out is below 1.7e-16 of the result);
+// the factor 2^k goes into the exponent bits (the result stays normal: exp(-40) = 2^-57.7).
+WSPR_HD double synth_exp(double x) {
+    const double invln2 = 1.44269504088896338700e+00;
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+    const double magic = 6755399441055744.0;               // 1.5 * 2^52: (t + magic) - magic = t rounded to an integer
+    const double fk = (x * invln2 + magic) - magic;
+    const double r = (x - fk * ln2_hi) - fk * ln2_lo;
+    double p = 1.0 / 479001600.0;
+    p = 1.0 / 39916800.0 + r * p;
+    p = 1.0 / 3628800.0 + r * p;
+    p = 1.0 / 362880.0 + r * p;
+    p = 1.0 / 40320.0 + r * p;
+    p = 1.0 / 5040.0 + r * p;
+    p = 1.0 / 720.0 + r * p;
+    p = 1.0 / 120.0 + r * p;
+    p = 1.0 / 24.0 + r * p;
+    p = 1.0 / 6.0 + r * p;
+    p = 0.5 + r * p;
+    p = 1.0 + r * p;
+    p = 1.0 + r * p;
+    union { uint64_t u; double d; } v;
+    v.d = p;
+    v.u += (uint64_t)(int64_t)(int)fk << 52;               // k <= 0: the shift is on the unsigned value
+    return v.d;
 }
 
 }  // namespace wspr

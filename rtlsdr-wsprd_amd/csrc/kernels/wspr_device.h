@@ -226,12 +226,20 @@ struct SynthTx {
     unsigned char symbols[kNSymD];
     unsigned char pad[2];
 };
+constexpr int kSynthCkptEvery = 64;                       // samples between phase checkpoints, layout [checkpoint][transmission]
 size_t synth_checkpoint_doubles(int ntx);                 // phase checkpoints of ntx transmissions
 // tx sorted by seg, seg_off[nseg + 1] its offsets per segment (both device memory); ckpt: synth_checkpoint_doubles(ntx)
 // doubles, first: ntx ints of scratch.  Rows of kIqStride floats, 16-byte aligned; without `accumulate` the whole row is
 // written (columns >= 45000 zero), with it those columns are left alone.
 void launch_synth(const SynthTx* tx, int ntx, const int* seg_off, int nseg, long long seg_index0, float sigma,
                   unsigned long long seed, int accumulate, double* ckpt, int* first, float* dI, float* dQ, hipStream_t st);
+void launch_synth_phase(const SynthTx* tx, int ntx, double* ckpt, int* first, hipStream_t st);   // launch_synth()'s first half
+// K13, the fading channel (k13_fade.hip; the definition in fade.h): launch_synth() with one FadeChannel (fade.h, derived on
+// the host by fade_path_setup()) per transmission in device memory.  Everything else as for launch_synth().
+struct FadeChannel;
+void launch_synth_faded(const SynthTx* tx, const FadeChannel* ch, int ntx, const int* seg_off, int nseg, long long seg_index0,
+                        float sigma, unsigned long long seed, int accumulate, double* ckpt, int* first, float* dI, float* dQ,
+                        hipStream_t st);
 void launch_normalise(float* dI, float* dQ, const int* n_valid, int nseg, int n_total, hipStream_t st);
 // resident input rows -> working rows (zero tail); false if the input is not 16-byte friendly
 bool launch_load_rows(const float* sI, const float* sQ, size_t stride, int samples, int nseg, float* dI, float* dQ,
