@@ -462,7 +462,10 @@ void subtract_signal2(float *id, float *qd, long np, float f0, int shift, float 
  * Fano, [34] and [35] the decodes it made at block size 2 and 3;
  * then the Doppler-spread stage (wspr_set_spread_estimate(); both zero while it is off), summed like the counts: [36] the
  * stage's device time, milliseconds (K11 with its transfers, taken without a host wait like the subtraction's), [37] the
- * spread jobs it ran (one per spot the call's decode loops added).
+ * spread jobs it ran (one per spot the call's decode loops added);
+ * then the list-decoding stage (wspr_set_message_list(); all zero while it is off), summed like the counts: [38] the
+ * stage's wall time, milliseconds (K14 and its round trips), [39] soft-symbol vectors it matched against the list, [40]
+ * the spots it accepted.
  * Returns the number of values written (<= capacity). */
 int wspr_last_timings(double *ms, int capacity);
 /* Worker threads of the library's host pools alive in this process (the threads that call into the library are
@@ -697,6 +700,69 @@ int wspr_spread_batch(const float *idat, const float *qdat, int nseg, int sample
                       const wspr_spread_item *items, int n, wspr_spread *out);
 int wspr_set_spread_estimate(int on);
 int wspr_last_spreads(wspr_spread *spreads, int capacity);
+/* List decoding against known messages (kernel K14), an opt-in second chance that uses the strongest prior a receiver
+ * farm has: the full text of what it decoded in the last hours -- WSPR beacons repeat the same 50 bits slot after slot.
+ * Correlating a failed candidate's soft symbols with the code word of every listed message is maximum-likelihood decoding
+ * over that list (JT65's "deep search", FT8's a-priori decoding).  The reference has nothing of the kind, so the definition
+ * is this library's own (rtlsdr-wsprd_amd/csrc/kernels/listmatch.h; tests/helpers/list_check.c is its serial form), all
+ * of it integer:
+ *   entry    a message text that get_wspr_channel_symbols() encodes on an empty hash memory and whose 11-byte decdata (as
+ *            fano() leaves it; obtained by decoding the noise-free code word) unpacks on an empty hash memory, WITHOUT a hash
+ *            look-up, to a canonical text that encodes to the same 162 symbols: message types 1 and 2 ("K1JT FN20 0" is
+ *            held as "K1JT FN20 00"); a type-3 text "<...>" is refused.  c[i] = 2 * (symbols[i] >> 1) - 1, i = 0 .. 161 in
+ *            transmission (interleaved) order; nothing is deinterleaved in this stage.
+ *   vector   162 soft symbols s[i] in transmission order, as wspr_fano_batch_device_wave() and wspr_osd_batch_device() take
+ *            them; v[i] = 2 s[i] - 255 (odd, never 0: the reliabilities of the ordered-statistics stage, signed).
+ *   score    S(m) = sum of c_m[i] * v[i] (int32) = R - 2 D, R = sum |v[i]|, D = the ordered-statistics cost of that code word.
+ *   winner   the largest S, ties to the lower list index; second = the largest S among all OTHER entries (INT32_MIN for a
+ *            list of one); V = sum of v[i]^2 (at most 10 534 050).
+ *   gate     accepted iff S1 > 0 and 256 * S1^2 >= zmin16^2 * V (int64): z = S1 / sqrt(V) >= zmin16 / 16.  z cannot exceed
+ *            sqrt(162) = 12.73, hence zmin16 = 1 .. 203.
+ *
+ * wspr_set_message_list(): process-wide, off by default.  messages[0 .. n) are the texts; n == 0 or messages == NULL
+ * switches the stage off (returns 0).  Entries whose 50 bits repeat an earlier entry are dropped, the first occurrence
+ * kept; returns the number of entries KEPT.  Returns -1 with a line on stderr naming the first offending index and CHANGES
+ * NOTHING (the list in force stays in force) for a text that does not qualify, n < 0, n > WSPR_LIST_MAX or zmin16 outside
+ * 1 .. 203.  A decode call reads the list once, on entry, as an immutable snapshot (like wspr_set_osd_depth(); the worker
+ * threads of a node-level call inherit it), so the setter may run beside decode calls; a WSPR_HASH_REVISIT call must run
+ * under the list (the very wspr_set_message_list() call) and zmin16 of the call it completes, and is refused otherwise.
+ * Every device context uploads the table (196 bytes per entry) on first use and replaces it when the list changes.
+ * wspr_message_list_entry(): what entry `index` of the list in force holds -- canonical text, decdata, channel symbols (any
+ * of the three may be NULL); -1 outside the list or with no list.
+ * wspr_list_match_batch_device(): K14 for n host vectors of 162 soft symbols against the list in force; out[i] = (winner,
+ * S1, second, V) of vector i, the gate left to the caller.  Returns 0; -1 with NOTHING WRITTEN without a usable device,
+ * without a list or for n < 0; n == 0 does nothing.
+ *
+ * While a list is set, every decode call runs the stage:
+ *   - the Fano budget split (wspr_set_fano_fast_budget) is off for the call -- results never depended on it;
+ *   - every candidate that was worth the jitter ladder (sync > minsync1) and decoded on none of its rungs -- nor in the
+ *     block-detection stage if that is on -- has its FIRST (rung-0) soft-symbol vector matched against the list.  The
+ *     sync/rms gate of wsprd.c:758 is NOT applied (it would remove about a third of the candidates this stage can use);
+ *     the list gate above replaces it and is decided at once, without a hash look-up;
+ *   - the stage runs AFTER the block-detection stage and BEFORE the ordered-statistics stage, which sees what it left;
+ *   - an accepted candidate is a decode like any other -- spot, hash store, subtraction, de-duplication, loop exits,
+ *     spread job -- reported with jitter 0 and CYCLES 1: the Fano search never reports fewer than 81 cycles and 0 marks an
+ *     ordered-statistics spot, so cycles == 1 marks a list spot.
+ * What to expect.  The stage reports ONLY listed messages, and what it reports is the list's text: A LISTED STATION THAT
+ * CHANGED ITS POWER (same call and locator, another dBm figure: code words that differ only through the last message
+ * bits) CAN BE REPORTED WITH ITS LISTED POWER.  Measured on one MI355X (tools/list_sensitivity.py, profiles/
+ * list_sensitivity.json; 2 048 synthetic single-signal segments per point, 8 192 entries): with the sent message absent and
+ * only that neighbour listed, 3 of the 1 041 vectors matched at -30 dB were reported as the neighbour at zmin16 = 96 (15 at
+ * 88, 1 at 104), none at -27 dB, where Fano decodes the true message.  With the sent messages listed the decoded share at
+ * zmin16 = 96 goes from 0.00 / 0.05 / 0.43 / 0.86 (stage off) to 0.33 / 0.76 / 0.92 / 0.93 at -32 / -31 / -30 / -29 dB,
+ * the same for 512 and 8 192 entries; the call's time does not change beyond its scatter, and K14 alone takes 0.15 ms for
+ * 2 048 vectors x 8 192 entries, 0.89 ms x 65 536.
+ * Recommended zmin16: 96 (z >= 6.0).  The Gaussian bound on a false accept per matched vector is M * Q(6.0) = 6e-5 for a
+ * full list of M = 65 536 entries; measured against that bound for the run's own M x vectors: noise alone 0 spots (1
+ * vector), unlisted messages 0 spots on 1 013 vectors (bound 0.008), a crowded scene of strong listed signals 0 on 68 (bound
+ * 0.0005) -- at 88 and 104 alike, so 96 stands.  The power confusion above is no noise event (the code words share all but
+ * the last message bits) and no tested threshold brings it under that bound: keep the list current.  The stage is OFF by
+ * default, and bench.py measures the default. */
+#define WSPR_LIST_MAX 65536
+typedef struct { int32_t index, score, second, v2; } wspr_list_match;   /* winner, S1, S2, V */
+int wspr_set_message_list(const char *const *messages, int n, int zmin16);
+int wspr_message_list_entry(int index, char text[23], unsigned char decdata[11], unsigned char symbols[162]);
+int wspr_list_match_batch_device(const unsigned char *symbols, int n, wspr_list_match *out);
 /* Library / device description, e.g. for bench logs. */
 const char *wspr_mi355x_version(void);
 int wspr_device_ready(void);        /* 1 if a HIP device and the kernels are usable */

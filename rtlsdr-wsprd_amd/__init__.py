@@ -149,6 +149,12 @@ def _bind(path):
     L.wspr_set_spread_estimate.restype = C.c_int
     L.wspr_last_spreads.argtypes = [C.c_void_p, C.c_int]
     L.wspr_last_spreads.restype = C.c_int
+    L.wspr_set_message_list.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.wspr_set_message_list.restype = C.c_int
+    L.wspr_message_list_entry.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wspr_message_list_entry.restype = C.c_int
+    L.wspr_list_match_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.wspr_list_match_batch_device.restype = C.c_int
     L.wspr_synth_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int,
                                           C.c_void_p, C.c_void_p]
     L.wspr_synth_batch_device.restype = C.c_int
@@ -328,6 +334,46 @@ def last_spreads(nseg, max_results, library=None):
     out = np.zeros((int(nseg), int(max_results)), SPREAD_DTYPE)
     n = (library or lib()).wspr_last_spreads(_ptr(out), int(out.size))
     return out if n == out.size else None
+
+
+LIST_MAX = 65536                   # include/wspr_mi355x.h: WSPR_LIST_MAX
+# include/wspr_mi355x.h: wspr_list_match, the result of K14 for one vector: winner, S1, S2, V
+LIST_MATCH_DTYPE = np.dtype([("index", "<i4"), ("score", "<i4"), ("second", "<i4"), ("v2", "<i4")])
+
+
+def set_message_list(messages, zmin16=96, library=None):
+    """wspr_set_message_list() of include/wspr_mi355x.h: the texts every later decode call matches its failed candidates
+    against (list decoding, K14), accepted at z >= zmin16 / 16.  None or an empty list switches the stage off (the
+    default).  Returns the number of entries kept (repeats are dropped), or -1 with NOTHING CHANGED for a text that does
+    not qualify, more than LIST_MAX texts, or zmin16 outside 1 .. 203.  The product and the lab library each keep their
+    own list: `library` (default: lib()) is the one set."""
+    L = library or lib()
+    msgs = [m if isinstance(m, bytes) else str(m).encode() for m in (messages or [])]
+    if not msgs:
+        return L.wspr_set_message_list(None, 0, int(zmin16))
+    arr = (C.c_char_p * len(msgs))(*msgs)
+    return L.wspr_set_message_list(C.cast(arr, C.c_void_p), len(msgs), int(zmin16))
+
+
+def message_list_entry(index, library=None):
+    """wspr_message_list_entry(): (canonical text, decdata uint8 [11], channel symbols uint8 [162]) of entry `index` of the
+    list in force, or None outside it."""
+    text = C.create_string_buffer(23)
+    dec, sym = np.zeros(11, np.uint8), np.zeros(NSYM, np.uint8)
+    if (library or lib()).wspr_message_list_entry(int(index), text, _ptr(dec), _ptr(sym)) != 0:
+        return None
+    return text.value.decode(), dec, sym
+
+
+def list_match(symbols, library=None):
+    """wspr_list_match_batch_device(): n vectors of 162 soft symbols (uint8 [n, 162], transmission order) against the list
+    in force.  Returns a LIST_MATCH_DTYPE array [n]; raises if the library refuses the call (no list, no device)."""
+    sym = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, NSYM)
+    out = np.zeros(sym.shape[0], LIST_MATCH_DTYPE)
+    rc = (library or lib()).wspr_list_match_batch_device(_ptr(sym), sym.shape[0], _ptr(out))
+    if rc != 0:
+        raise RuntimeError("wspr_list_match_batch_device failed (rc %d: no list set, or no usable HIP device)" % rc)
+    return out
 
 
 def get_wspr_channel_symbols(message):
@@ -567,7 +613,8 @@ TIMING_NAMES = (
     "cpu_ms_subtract", "cpu_ms_finish", "message_cache_lookups", "message_cache_hits",
     "osd_ms", "osd_vectors", "osd_spots", "lag_pruned", "lag_exact_evals", "lag_fallbacks",
     "block_ms", "block_vectors", "block2_decodes", "block3_decodes",
-    "spread_ms", "spread_jobs")
+    "spread_ms", "spread_jobs",
+    "list_ms", "list_vectors", "list_spots")
 
 
 def last_timings():

@@ -29,7 +29,7 @@ compile_variant() {
       pids+=($!)
     fi
   done
-  for s in wspr_message wspr_hashmem wspr_wav; do   # pure host C++ (no HIP): the message layer, the batch hash memory, the WAV reader
+  for s in wspr_message wspr_hashmem wspr_wav wspr_msglist; do   # pure host C++ (no HIP): the message layer, the batch hash memory, the WAV reader, the message list of K14
     o="$objdir/$s.o"
     objs+=("$o")
     if [ ! -f "$o" ] || [ "$here/host/$s.cpp" -nt "$o" ] || [ -n "$(find "$here/host" -name '*.h' -newer "$o" | head -1)" ]; then

@@ -2,9 +2,12 @@
 // and the statistics of the last call.
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <exception>
+#include <memory>
 
 #include "wspr_capi_impl.h"
+#include "../kernels/listmatch.h"
 #include "../kernels/osd.h"
 
 using wspr::Context;
@@ -94,6 +97,47 @@ int wspr_osd_batch_device(const unsigned char* symbols, int n, int depth, unsign
 int wspr_set_block_detection(int maxblock) {
     if (maxblock < 1 || maxblock > 3) return -2;
     return wspr::block_setting().exchange(maxblock);
+}
+
+int wspr_set_message_list(const char* const* messages, int n, int zmin16) {
+    if (!messages || n == 0) {                             // the stage off
+        wspr::set_message_list_setting(nullptr);
+        return 0;
+    }
+    int bad = -1;
+    std::shared_ptr<const wspr::MessageList> list = wspr::build_message_list(messages, n, zmin16, &bad);
+    if (!list) {
+        if (bad >= 0)
+            fprintf(stderr, "libwspr_mi355x: wspr_set_message_list: entry %d is not a message this stage can hold "
+                            "(a type-1 or type-2 text that encodes and decodes to itself without a hash look-up)\n", bad);
+        else
+            fprintf(stderr, "libwspr_mi355x: wspr_set_message_list: %d entries (0 .. %d) and zmin16 = %d (%d .. %d) refused\n", n,
+                    wspr::listmatch::kMaxEntries, zmin16, wspr::listmatch::kZminLo, wspr::listmatch::kZminHi);
+        return -1;                                         // the list in force stays in force
+    }
+    const int kept = list->n;
+    wspr::set_message_list_setting(std::move(list));
+    return kept;
+}
+
+int wspr_message_list_entry(int index, char text[23], unsigned char decdata[11], unsigned char symbols[162]) {
+    const std::shared_ptr<const wspr::MessageList> list = wspr::message_list_setting();
+    if (!list || index < 0 || index >= list->n) return -1;
+    if (text) memcpy(text, list->text.data() + (size_t)index * 23, 23);
+    if (decdata) memcpy(decdata, list->decdata.data() + (size_t)index * 11, 11);
+    if (symbols) memcpy(symbols, list->symbols.data() + (size_t)index * 162, 162);
+    return 0;
+}
+
+int wspr_list_match_batch_device(const unsigned char* symbols, int n, wspr_list_match* out) {
+    if (n < 0) return -1;
+    LaneTurn lane_turn;                                    // takes the snapshot of the list, like a decode call
+    const std::shared_ptr<const wspr::MessageList> list = wspr::call_list();
+    if (!list) return -1;
+    if (n == 0) return 0;
+    try {
+        return Context::get().list_batch(symbols, n, *list, out);
+    } catch (const std::exception& e) { return fail("wspr_list_match_batch_device", e); }
 }
 
 int wspr_host_pool_workers(void) { return wspr::pool_workers_alive().load(); }

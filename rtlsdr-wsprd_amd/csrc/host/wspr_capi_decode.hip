@@ -50,6 +50,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
     Context& c0 = Context::get();
     const int dev = c0.device(), lane = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
               maxblock = wspr::call_maxblock(), spread_on = wspr::call_spread();
+    const std::shared_ptr<const wspr::MessageList> msg_list = wspr::call_list();
     // wspr_last_spreads(): the calling thread's record takes the layout of `decodes`; a revisit of the same layout keeps
     // the entries of the segments it does not decode again.  The traced form does not record.
     wspr::LastSpreads& last = wspr::last_spreads_of_thread();
@@ -77,6 +78,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
                     wspr::OsdScope call_osd(osd_depth);
                     wspr::BlockScope call_block(maxblock);
                     wspr::SpreadScope call_spread(spread_on);
+                    wspr::ListScope call_list(msg_list);
                     if (hipSetDevice(dev) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
                     Context::bind_lane(lane);
                     fn(g, Context::slot(g));
@@ -184,7 +186,9 @@ int decode_hashed(int nseg, int samples, const decoder_options& options, decoder
     const int nslots_now = (nseg >= 128) ? Context::slot_cap() : 1;
     if (revisit && !(t_hash && t_hash->valid && (int)t_hash->log.size() == nseg && t_hash->seg0 == seg_index0 &&
                      t_hash->samples == samples && t_hash->nslots == nslots_now && t_hash->arith == wspr::call_arith() &&
-                     t_hash->osd_depth == wspr::call_osd_depth() && t_hash->maxblock == wspr::call_maxblock()))
+                     t_hash->osd_depth == wspr::call_osd_depth() && t_hash->maxblock == wspr::call_maxblock() &&
+                     t_hash->list_gen == wspr::call_list_generation() &&
+                     t_hash->list_zmin16 == (wspr::call_list() ? wspr::call_list()->zmin16 : 0)))
         throw std::runtime_error("WSPR_HASH_REVISIT without a matching, completed previous call on this thread");
     if (!revisit) {
         t_hash.reset(new wspr::HashBatch);
@@ -193,6 +197,8 @@ int decode_hashed(int nseg, int samples, const decoder_options& options, decoder
         t_hash->arith = wspr::call_arith();
         t_hash->osd_depth = wspr::call_osd_depth();
         t_hash->maxblock = wspr::call_maxblock();
+        t_hash->list_gen = wspr::call_list_generation();
+        t_hash->list_zmin16 = wspr::call_list() ? wspr::call_list()->zmin16 : 0;
         t_hash->resize(nseg);
     }
     wspr::HashBatch& hb = *t_hash;

@@ -297,6 +297,7 @@ int wspr_session_decode_many(wspr_session* const* sessions, const int* buffers, 
     wspr::ArithScope call_mode;            // one mode for every group of options this call decodes
     wspr::OsdScope call_osd;               // and one ordered-statistics depth
     wspr::BlockScope call_block;           // and one block-detection setting
+    wspr::ListScope call_list;             // and one message list
     for (int k = 0; k < n; ++k) {
         n_results[k] = 0;
         if (decoded) decoded[k] = 0;

@@ -49,6 +49,7 @@ struct LaneTurn {                                  // the calling thread's lane 
     wspr::OsdScope osd;                            // ... and wspr_set_osd_depth()
     wspr::BlockScope block;                        // ... and wspr_set_block_detection()
     wspr::SpreadScope spread;                      // ... and wspr_set_spread_estimate()
+    wspr::ListScope list;                          // ... and the list of wspr_set_message_list()
     std::unique_lock<std::recursive_mutex> hold;
     LaneTurn() : hold(lane_turn_of(current_device_or_0(), Context::lane())) {}
 };

@@ -79,6 +79,8 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
     wspr::ArithScope call_mode;
     wspr::OsdScope call_osd;
     wspr::BlockScope call_block;
+    wspr::ListScope call_list;
+    const std::shared_ptr<const wspr::MessageList> msg_list = wspr::call_list();
     const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
               maxblock = wspr::call_maxblock();
     int home = 0;
@@ -93,6 +95,7 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
             wspr::ArithScope worker_mode(arith);
             wspr::OsdScope worker_osd(osd_depth);
             wspr::BlockScope worker_block(maxblock);
+            wspr::ListScope worker_list(msg_list);
             if (hipSetDevice(k % count) != hipSuccess) {
                 rcs[k] = -1;
                 for (int s = lo; s < hi; ++s) n_results[s] = 0;
@@ -149,6 +152,8 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
     wspr::ArithScope call_mode;
     wspr::OsdScope call_osd;
     wspr::BlockScope call_block;
+    wspr::ListScope call_list;
+    const std::shared_ptr<const wspr::MessageList> msg_list = wspr::call_list();
     const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
               maxblock = wspr::call_maxblock();
     std::vector<int> rcs(ndevices, 0);
@@ -161,6 +166,7 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
             wspr::ArithScope worker_mode(arith);
             wspr::OsdScope worker_osd(osd_depth);
             wspr::BlockScope worker_block(maxblock);
+            wspr::ListScope worker_list(msg_list);
             const int dev = k % count;
             if (hipSetDevice(dev) != hipSuccess) { rcs[k] = -1; return; }
             Context::bind_lane(lane0 + k / count);

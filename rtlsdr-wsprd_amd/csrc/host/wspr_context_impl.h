@@ -22,6 +22,7 @@
 
 #include "wspr_message.h"
 #include "../kernels/osd.h"
+#include "../kernels/listmatch.h"
 #include "../kernels/spread.h"
 
 namespace wspr {
@@ -253,6 +254,9 @@ struct Context::Impl {
     PinBuf h_fz;                     // K6w's results on their way to the host (a copy into pageable memory would make
                                      // the runtime wait for the search itself, on a CPU)
     PinBuf h_osd;                    // K9's results on their way to the host
+    DevBuf t_list, list_out;         // K14: the list's table [48][padded(M)] words + B[padded(M)], and one ListMatch per vector
+    uint64_t list_gen = 0;           // ... the generation of the list t_list holds (0: none)
+    PinBuf h_list;                   // ... the results on their way to the host
     DevBuf blk_hyp, blk_out;         // K10: the hypotheses, and [sync | rms | symbols] of each
     PinBuf h_blk;                    // ... on their way to the host
     DevBuf spr_tw, spr_jobs, spr_ckpt, spr_out;   // K11: twiddles (built on first use), jobs, phase checkpoints, 4 words per job

@@ -47,6 +47,8 @@ struct HashBatch {
     int arith = 0;                                  // wspr_set_arithmetic() mode of the call (a revisit must match it)
     int osd_depth = -1;                             // wspr_set_osd_depth() of the call (a revisit must match it too)
     int maxblock = 1;                               // wspr_set_block_detection() of the call (likewise)
+    unsigned long long list_gen = 0;                // wspr_set_message_list() of the call: the list's generation (0: off) ...
+    int list_zmin16 = 0;                            // ... and its zmin16 (likewise)
 
     HashBatch();
     void load_file();                               // hashtable.txt of the working directory (wsprd.c:481-494)

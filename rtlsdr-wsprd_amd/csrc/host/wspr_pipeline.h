@@ -13,6 +13,7 @@
 #include "../../../include/wspr_mi355x_bench.h"   // declarations only: the definitions exist in the lab build (-DWSPR_LAB)
 #include "../kernels/wspr_device.h"
 #include "wspr_hashmem.h"
+#include "wspr_msglist.h"
 
 namespace wspr {
 
@@ -112,6 +113,7 @@ enum TimingSlot : int {
     kTmLagPruned, kTmLagExactEvals, kTmLagFallbacks,
     kTmBlockMs, kTmBlockVectors, kTmBlock2Decodes, kTmBlock3Decodes,
     kTmSpreadMs, kTmSpreadJobs,
+    kTmListMs, kTmListVectors, kTmListSpots,
     kTimingSlots
 };
 // A batch runs on several pipelines at once and each keeps its own values; wspr_last_timings() folds them.  The stage
@@ -119,7 +121,7 @@ enum TimingSlot : int {
 // from it on is SUMMED -- the counts, and the CPU times kTmCpuMs* as well (CPU time spent on different threads adds
 // up; the public header says "summed over the slots").
 constexpr int kTimingFirstSummed = kTmFanoCalls;
-static_assert(kTimingSlots == 38 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
+static_assert(kTimingSlots == 41 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
 
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt
@@ -221,6 +223,10 @@ public:
                   unsigned* order);
     int osd_resident(const unsigned char* d_symbols, const int* h_offsets, int n, int depth, unsigned char* data,
                      unsigned* dist, unsigned* nhard, unsigned* order);
+    // K14 (k14_list.hip; the definition in kernels/listmatch.h) over host vectors, and over vectors already in HBM (vector i
+    // at d_symbols + h_offsets[i] * 162) against `list`, whose table this context uploads on first use; results on the host
+    int list_batch(const unsigned char* symbols, int n, const MessageList& list, wspr_list_match* out);
+    int list_resident(const unsigned char* d_symbols, const int* h_offsets, int n, const MessageList& list, wspr_list_match* out);
     // K10 (k10_blockdemod.hip; the definition in kernels/blockdemod.h): the vectors of block sizes 1, 2, 3 of n hypotheses,
     // on the working rows (results on the host; rms n*3, sync n and d_symbols may be null) and over host rows
     int block_resident(const BlockHyp* hyps, int n, int samples, unsigned char* symbols, float* rms_out, float* sync_out,

@@ -273,8 +273,9 @@ int Context::decode_resident(int nseg, int samples, const decoder_options& opt, 
     // (a shared hash memory keeps the host's full budget too: a provisional failure would log look-ups of a decode
     // that is thrown away)
     // (and so does the ordered-statistics stage: it takes the candidates whose every Fano attempt FAILED, which a
-    // provisional failure is not; the block-detection stage likewise)
-    const unsigned fast = (reload && nseg >= 256 && !dev_fano && !trace && !hb && call_osd_depth() < 0 && call_maxblock() <= 1)
+    // provisional failure is not; the block-detection and the list-decoding stage likewise)
+    const unsigned fast = (reload && nseg >= 256 && !dev_fano && !trace && !hb && call_osd_depth() < 0 && call_maxblock() <= 1 &&
+                           !call_list())
                               ? std::min(fast_cfg, 10000u) : 0u;
     if (trace) memset(trace, 0, (size_t)nseg * sizeof(wspr_trace));
     d->dev_fano = dev_fano;
@@ -351,6 +352,10 @@ struct Context::DecodeRun {
     const int maxblock = call_maxblock();
     std::vector<unsigned char> by_block;
     std::atomic<long> n_block_decodes[2] = {{0}, {0}};   // consumed decodes by block size 2 and 3
+    // wspr_set_message_list() of this call (null: off), and per item of the current wave: its decode is the list stage's
+    const std::shared_ptr<const MessageList> list = call_list();
+    std::vector<char> by_list;
+    std::atomic<long> n_list_spots{0};        // consumed decodes of the stage
     // wspr_set_spread_estimate() of this call.  keep_books() leaves the wave's jobs here (one per decode that added a
     // spot) with the place of each result among the segment's spots; launch_spreads() queues them ahead of the wave's
     // subtraction, collect_spreads() files the results once the stream has passed them.
@@ -443,6 +448,7 @@ struct Context::DecodeRun {
     void refine_and_first_rung(std::vector<WaveItem>& wave);
     void remaining_rungs(std::vector<WaveItem>& wave);
     void block_rescue(std::vector<WaveItem>& wave);
+    void list_rescue(std::vector<WaveItem>& wave);
     void osd_rescue(std::vector<WaveItem>& wave);
     std::vector<SubJob> keep_books(std::vector<WaveItem>& wave);
     void subtract(const std::vector<SubJob>& jobs);
@@ -645,6 +651,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
         const int* cnt = reinterpret_cast<const int*>(h_down + o_cnt);
         c.t_ms[kTmLagExactEvals] += cnt[0]; c.t_ms[kTmLagFallbacks] += cnt[1]; c.t_ms[kTmLagPruned] += cnt[2];
     }
+    if (list) this->d_sym0 = d_sym0;                           // the list stage matches the rung-0 vectors where they lie
     if (osd_depth >= 0) {                                      // the rescue stage needs these after the ladder reused the block
         this->d_sym0 = d_sym0;
         gate0.resize(nw);
@@ -933,6 +940,34 @@ void Context::DecodeRun::block_rescue(std::vector<WaveItem>& wave) {
     c.t_ms[kTmBlockMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
+// List decoding against known messages (wspr_set_message_list(); the definition in kernels/listmatch.h): every candidate of
+// the wave that was worth a ladder and decoded on none of its rungs (nor in the block stage) has its rung-0 vector matched
+// against the call's list by K14, straight from the rung-0 symbols in HBM.  No sync/rms gate: the list gate decides, at
+// once and without a hash look-up.  An accepted candidate takes the entry's decdata and is a decode like any other;
+// cycles == 1 marks it (Fano: >= 81, the ordered-statistics stage: 0).
+void Context::DecodeRun::list_rescue(std::vector<WaveItem>& wave) {
+    const int nw = (int)wave.size();
+    by_list.assign(nw, 0);
+    std::vector<int> att;
+    for (int i = 0; i < nw; ++i)
+        if (wave[i].worth && !wave[i].decoded) att.push_back(i);
+    if (att.empty()) return;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int na = (int)att.size();
+    std::vector<wspr_list_match> res(na);
+    ctx.list_resident(d_sym0, att.data(), na, *list, res.data());
+    for (int k = 0; k < na; ++k) {
+        const wspr_list_match& r = res[k];
+        if (r.index < 0 || r.index >= list->n || !listmatch::gate(r.score, r.v2, list->zmin16)) continue;
+        WaveItem& w = wave[att[k]];
+        by_list[att[k]] = 1;
+        w.decoded = true; w.jitter = 0; w.cycles = 1;
+        memcpy(w.decdata, list->decdata.data() + (size_t)r.index * 11, 11);
+    }
+    c.t_ms[kTmListMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    c.t_ms[kTmListVectors] += (double)na;
+}
+
 // Ordered-statistics rescue (wspr_set_osd_depth() >= 0): every candidate of the wave that was worth a ladder, whose
 // every Fano attempt failed and whose rung-0 vector passed the sync/rms gate goes through K9, straight from the rung-0
 // symbols in HBM (the ladder's upload only rewrote the head of that block, the items).  The result is provisional: it
@@ -1017,6 +1052,7 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
         }
         if (!(w.worth && w.decoded)) continue;
         if (maxblock > 1 && by_block[i]) n_block_decodes[by_block[i] - 2]++;
+        if (list && by_list[i]) n_list_spots++;
 
         signed char message[12] = {0};
         for (int k = 0; k < 11; ++k) message[k] = (signed char)w.decdata[k];
@@ -1256,6 +1292,7 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
             { CpuSpan sp(&d->t_ms[kTmCpuMsRefine]); run.refine_and_first_rung(wave); }
             { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.remaining_rungs(wave); }
             if (run.maxblock > 1) { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.block_rescue(wave); }
+            if (run.list) { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.list_rescue(wave); }
             if (run.osd_depth >= 0) { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.osd_rescue(wave); }
             std::vector<SubJob> jobs;
             { CpuSpan sp(&d->t_ms[kTmCpuMsBooks]); jobs = run.keep_books(wave); }
@@ -1265,6 +1302,7 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
     }
     { CpuSpan sp(&d->t_ms[kTmCpuMsFinish]); run.finish(active0, n_results); }
     d->t_ms[kTmOsdSpots] += (double)run.n_osd_spots.load();
+    d->t_ms[kTmListSpots] += (double)run.n_list_spots.load();
     d->t_ms[kTmBlock2Decodes] += (double)run.n_block_decodes[0].load();
     d->t_ms[kTmBlock3Decodes] += (double)run.n_block_decodes[1].load();
     guard.armed = false;
@@ -1521,6 +1559,55 @@ int Context::osd_resident(const unsigned char* d_symbols, const int* h_offsets, 
     memcpy(order, hout + (size_t)n * 8, (size_t)n * 4);
     memcpy(data, hout + o_data, (size_t)n * 11);
     return 0;
+}
+
+// K14 over vectors that are already in HBM (the decode loop's list stage): vector i is the 162 soft symbols at
+// d_symbols + h_offsets[i] * 162, transmission order, against `list`.  The list's table goes up on first use and stays
+// until a call brings another list (its generation tells).  Results on the host.
+int Context::list_resident(const unsigned char* d_symbols, const int* h_offsets, int n, const MessageList& list,
+                           wspr_list_match* out) {
+    static_assert(sizeof(ListMatch) == sizeof(wspr_list_match), "public and internal result layouts differ");
+    Impl& c = *d;
+    if (n <= 0 || list.n <= 0) return 0;
+    const int mpad = listmatch::padded(list.n);
+    const size_t tab_bytes = (size_t)listmatch::kWords * mpad * 4, bias_bytes = (size_t)mpad * 4;
+    if (c.list_gen != list.generation) {
+        c.list_gen = 0;
+        // over the table of the list no longer in force (the buffer only grows: freeing device memory waits for the whole
+        // device, the other pipelines' kernels included)
+        char* t = static_cast<char*>(c.t_list.need(tab_bytes + bias_bytes));
+        // pageable sources: both copies have left the host when the calls return
+        upload(t, list.table.data(), tab_bytes, c.stream);
+        upload(t + tab_bytes, list.bias.data(), bias_bytes, c.stream);
+        HIP_OK(hipStreamSynchronize(c.stream));
+        c.list_gen = list.generation;
+    }
+    const char* t = c.t_list.as<char>();
+    int* h_off = static_cast<int*>(c.h_misc.need((size_t)n * 4));
+    memcpy(h_off, h_offsets, (size_t)n * 4);
+    int* doff = static_cast<int*>(c.fz_off.need((size_t)n * 4));
+    const size_t blk = (size_t)n * sizeof(ListMatch);
+    ListMatch* dout = static_cast<ListMatch*>(c.list_out.need(blk));
+    char* hout = static_cast<char*>(c.h_list.need(blk));
+    upload(doff, h_off, (size_t)n * 4, c.stream);
+    launch_list_match(d_symbols, doff, n, reinterpret_cast<const int*>(t), reinterpret_cast<const int*>(t + tab_bytes), list.n,
+                      dout, c.stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(hout, dout, blk, hipMemcpyDeviceToHost, c.stream));
+    sync();
+    memcpy(out, hout, blk);
+    return 0;
+}
+
+// K14 over n host vectors (wspr_list_match_batch_device)
+int Context::list_batch(const unsigned char* symbols, int n, const MessageList& list, wspr_list_match* out) {
+    Impl& c = *d;
+    if (n <= 0) return 0;
+    unsigned char* dsym = static_cast<unsigned char*>(c.fz_sym.need((size_t)n * kNSymD));
+    upload(dsym, symbols, (size_t)n * kNSymD, c.stream);
+    std::vector<int> off(n);
+    for (int i = 0; i < n; ++i) off[i] = i;
+    return list_resident(dsym, off.data(), n, list, out);
 }
 
 // K9 over n host vectors (wspr_osd_batch_device)

@@ -263,5 +263,14 @@ void launch_decimate(const uint8_t* raw, size_t bytes_per_seg, int nseg, float* 
 // into rows of kIqStride floats, the whole row written (zero from min(ceil(nsamp / 32), 45000) on).
 void launch_audio_front(const int16_t* pcm, size_t pcm_stride, int nsamp, int nseg, float* dI, float* dQ, hipStream_t st);
 void audio_front_taps(float* gi511, float* gq511);                  // the two tap tables of audio_front.h as floats
+// K14, list decoding against known messages (k14_list.hip; the definition in listmatch.h): vector i = the 162 soft symbols at
+// symbols + offsets[i] * 162 (transmission order) against the m listed code words.  table: 48 x padded(m) words of four int8
+// chips, word-major, zero beyond position 161 and beyond entry m - 1; bias: B of each entry.  ListMatch is wspr_list_match
+// of the public header: one per vector.
+struct ListMatch {
+    int32_t index, score, second, v2;
+};
+void launch_list_match(const unsigned char* symbols, const int* offsets, int n, const int* table, const int* bias, int m,
+                       ListMatch* out, hipStream_t st);
 
 }  // namespace wspr
