@@ -48,9 +48,9 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
     const int nslots = (nseg >= 128) ? Context::slot_cap() : 1;
     Context::note_slots_used(nslots);
     Context& c0 = Context::get();
-    const int dev = c0.device(), lane = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
-              maxblock = wspr::call_maxblock(), spread_on = wspr::call_spread();
-    const std::shared_ptr<const wspr::MessageList> msg_list = wspr::call_list();
+    const int dev = c0.device(), lane = Context::lane();
+    const wspr::CallSettings settings = wspr::call_settings();
+    const int spread_on = settings.spread;
     // wspr_last_spreads(): the calling thread's record takes the layout of `decodes`; a revisit of the same layout keeps
     // the entries of the segments it does not decode again.  The traced form does not record.
     wspr::LastSpreads& last = wspr::last_spreads_of_thread();
@@ -74,11 +74,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
         for (int g = 0; g < nslots; ++g)
             th.emplace_back([&, g] {
                 try {
-                    wspr::ArithScope call_mode(arith);
-                    wspr::OsdScope call_osd(osd_depth);
-                    wspr::BlockScope call_block(maxblock);
-                    wspr::SpreadScope call_spread(spread_on);
-                    wspr::ListScope call_list(msg_list);
+                    wspr::CallScope call_scope(settings);
                     if (hipSetDevice(dev) != hipSuccess) throw std::runtime_error("hipSetDevice failed");
                     Context::bind_lane(lane);
                     fn(g, Context::slot(g));

@@ -294,10 +294,7 @@ int wspr_session_decode_many(wspr_session* const* sessions, const int* buffers, 
                              int max_results, int* n_results, int* decoded) {
     wspr::NoSpreadRecord no_record;
     if (!sessions || !buffers || n < 0 || !decodes || max_results < 1 || !n_results) return -1;
-    wspr::ArithScope call_mode;            // one mode for every group of options this call decodes
-    wspr::OsdScope call_osd;               // and one ordered-statistics depth
-    wspr::BlockScope call_block;           // and one block-detection setting
-    wspr::ListScope call_list;             // and one message list
+    wspr::CallScope call_scope;            // one set of settings for every group of options this call decodes
     for (int k = 0; k < n; ++k) {
         n_results[k] = 0;
         if (decoded) decoded[k] = 0;

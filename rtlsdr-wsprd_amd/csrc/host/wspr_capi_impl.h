@@ -45,11 +45,7 @@ inline int current_device_or_0() {
     return dev;
 }
 struct LaneTurn {                                  // the calling thread's lane of the current device
-    wspr::ArithScope arith;                        // the outermost entry point reads wspr_set_arithmetic() here, once
-    wspr::OsdScope osd;                            // ... and wspr_set_osd_depth()
-    wspr::BlockScope block;                        // ... and wspr_set_block_detection()
-    wspr::SpreadScope spread;                      // ... and wspr_set_spread_estimate()
-    wspr::ListScope list;                          // ... and the list of wspr_set_message_list()
+    wspr::CallScope settings;                      // the outermost entry point reads the call's settings here, once
     std::unique_lock<std::recursive_mutex> hold;
     LaneTurn() : hold(lane_turn_of(current_device_or_0(), Context::lane())) {}
 };

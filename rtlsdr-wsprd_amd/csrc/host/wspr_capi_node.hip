@@ -76,13 +76,9 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
     if (options.usehashtable && nseg > 1)                // ordered by definition: nothing to spread
         return wspr_decode_batch(idat, qdat, nseg, samples, seg_stride, options, decodes, max_results, n_results, 0);
     NodeShareGuard share(ndevices);
-    wspr::ArithScope call_mode;
-    wspr::OsdScope call_osd;
-    wspr::BlockScope call_block;
-    wspr::ListScope call_list;
-    const std::shared_ptr<const wspr::MessageList> msg_list = wspr::call_list();
-    const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
-              maxblock = wspr::call_maxblock();
+    wspr::CallScope call_scope;
+    const wspr::CallSettings settings = wspr::call_settings();
+    const int lane0 = Context::lane();
     int home = 0;
     (void)hipGetDevice(&home);
     std::vector<int> rcs(ndevices, 0);
@@ -92,10 +88,7 @@ int wspr_decode_batch_node(float* idat, float* qdat, int nseg, int samples, size
         wspr_shard_range(nseg, k, ndevices, &lo, &hi);
         if (hi <= lo) continue;
         th.emplace_back([=, &rcs] {
-            wspr::ArithScope worker_mode(arith);
-            wspr::OsdScope worker_osd(osd_depth);
-            wspr::BlockScope worker_block(maxblock);
-            wspr::ListScope worker_list(msg_list);
+            wspr::CallScope worker_scope(settings);
             if (hipSetDevice(k % count) != hipSuccess) {
                 rcs[k] = -1;
                 for (int s = lo; s < hi; ++s) n_results[s] = 0;
@@ -149,13 +142,9 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
         return rc;
     }
     NodeShareGuard share(ndevices);
-    wspr::ArithScope call_mode;
-    wspr::OsdScope call_osd;
-    wspr::BlockScope call_block;
-    wspr::ListScope call_list;
-    const std::shared_ptr<const wspr::MessageList> msg_list = wspr::call_list();
-    const int lane0 = Context::lane(), arith = wspr::call_arith(), osd_depth = wspr::call_osd_depth(),
-              maxblock = wspr::call_maxblock();
+    wspr::CallScope call_scope;
+    const wspr::CallSettings settings = wspr::call_settings();
+    const int lane0 = Context::lane();
     std::vector<int> rcs(ndevices, 0);
     std::vector<std::thread> th;
     for (int k = 0; k < ndevices; ++k) {
@@ -163,10 +152,7 @@ int wspr_decode_batch_node_device(const void* d_idat, const void* d_qdat, int sr
         wspr_shard_range(nseg, k, ndevices, &lo, &hi);
         if (hi <= lo) continue;
         th.emplace_back([=, &rcs] {
-            wspr::ArithScope worker_mode(arith);
-            wspr::OsdScope worker_osd(osd_depth);
-            wspr::BlockScope worker_block(maxblock);
-            wspr::ListScope worker_list(msg_list);
+            wspr::CallScope worker_scope(settings);
             const int dev = k % count;
             if (hipSetDevice(dev) != hipSuccess) { rcs[k] = -1; return; }
             Context::bind_lane(lane0 + k / count);

@@ -145,10 +145,11 @@ public:
         for (auto& t : workers_) t.join();
     }
     // runs fn(i) for i in [0, n); the calling thread participates.
-    // chunk = indices handed out per grab; 0 = automatic (many cheap, uniform tasks)
+    // chunk = indices handed out per grab; 0 = automatic (many cheap, uniform tasks); 1 = tasks that may take
+    // milliseconds each (Fano attempts): worth the workers from two tasks on
     void run(int n, const std::function<void(int)>& fn, int chunk = 0) {
         if (n <= 0) return;
-        if (workers_.empty() || n < 4) { for (int i = 0; i < n; ++i) fn(i); return; }
+        if (workers_.empty() || n < (chunk == 1 ? 2 : 4)) { for (int i = 0; i < n; ++i) fn(i); return; }
         auto job = std::make_shared<Job>();
         job->fn = &fn;
         job->total = n;
@@ -283,6 +284,8 @@ struct Context::Impl {
     size_t hash_arena_segs = 0;
     double t_ms[kTimingSlots] = {0};           // stage times (ms), Fano statistics and host CPU time by phase of the last batch
     std::atomic<long> n_fano{0}, n_timeout{0}, n_cycles{0}, n_kept{0}, n_subjobs{0}, n_mc_lookups{0}, n_mc_hits{0};
+    // one Fano attempt into the three counts; WHICH attempts count is each call site's rule
+    void count_fano(int ret, unsigned cycles) { n_fano++; n_cycles += cycles; if (ret) n_timeout++; }
     bool blocking = false;
     hipEvent_t ev_sync = nullptr;
     hipEvent_t ev[2] = {nullptr, nullptr};

@@ -99,9 +99,4 @@ void set_message_list_setting(std::shared_ptr<const MessageList> list) {
     g_list = std::move(list);
 }
 
-ListSlot& call_list_slot() {
-    thread_local ListSlot s;
-    return s;
-}
-
 }  // namespace wspr

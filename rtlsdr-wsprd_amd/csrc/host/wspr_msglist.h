@@ -27,24 +27,6 @@ std::shared_ptr<const MessageList> build_message_list(const char* const* message
 // The process-wide list (null: the stage is off) ...
 std::shared_ptr<const MessageList> message_list_setting();
 void set_message_list_setting(std::shared_ptr<const MessageList> list);
-// ... and the snapshot of the current call, read ONCE on entry and handed to the threads a call starts for itself, exactly
-// as the settings of wspr_pipeline.h (ArithScope, OsdScope).
-struct ListSlot { bool set = false; std::shared_ptr<const MessageList> list; };
-ListSlot& call_list_slot();                         // thread-local
-inline std::shared_ptr<const MessageList> call_list() {
-    const ListSlot& s = call_list_slot();
-    return s.set ? s.list : message_list_setting();
-}
-inline uint64_t call_list_generation() { const auto l = call_list(); return l ? l->generation : 0; }
-struct ListScope {
-    bool owner;
-    ListScope() : owner(!call_list_slot().set) { if (owner) { call_list_slot().list = message_list_setting(); call_list_slot().set = true; } }
-    explicit ListScope(std::shared_ptr<const MessageList> l) : owner(!call_list_slot().set) {
-        if (owner) { call_list_slot().list = std::move(l); call_list_slot().set = true; }
-    }
-    ~ListScope() { if (owner) { call_list_slot().list.reset(); call_list_slot().set = false; } }
-    ListScope(const ListScope&) = delete;
-    ListScope& operator=(const ListScope&) = delete;
-};
+// ... of which a decode call takes a snapshot on entry, with its other settings (CallSettings in wspr_pipeline.h)
 
 }  // namespace wspr

@@ -29,62 +29,41 @@ std::atomic<int>& node_share();
 // CUs the front end (K0) may occupy, 0 = all (wspr_set_front_end_cus / WSPR_K0_CUS)
 std::atomic<int>& front_end_cus();
 
-// wspr_set_arithmetic(): the process-wide mode (0 exact, 1 contracted).  A call reads it ONCE, on entry (ArithScope in
-// the outermost entry point of the calling thread), and every launch of that call uses call_arith(); threads a call
-// starts for itself (slots, node workers) install the caller's value with ArithScope(mode).
+// The five process-wide settings a decode call honours: wspr_set_arithmetic() (0 exact, 1 contracted),
+// wspr_set_osd_depth() (-1 off, 0..3), wspr_set_block_detection() (1 off, 2, 3), wspr_set_spread_estimate() (0 off, 1 on)
+// and the list of wspr_set_message_list() (null: off; message_list_setting() in wspr_msglist.h).
 std::atomic<int>& arith_setting();
-int& call_arith_slot();                                   // thread-local: the current call's mode, -1 outside a call
-inline int call_arith() { const int m = call_arith_slot(); return m < 0 ? arith_setting().load() : m; }
-struct ArithScope {
-    bool owner;
-    ArithScope() : owner(call_arith_slot() < 0) { if (owner) call_arith_slot() = arith_setting().load(); }
-    explicit ArithScope(int mode) : owner(call_arith_slot() < 0) { if (owner) call_arith_slot() = mode; }
-    ~ArithScope() { if (owner) call_arith_slot() = -1; }
-    ArithScope(const ArithScope&) = delete;
-    ArithScope& operator=(const ArithScope&) = delete;
-};
-
-// wspr_set_osd_depth(): the process-wide depth of the ordered-statistics rescue stage (-1 off, 0..3).  Read ONCE per
-// call, on entry, and handed to the threads a call starts for itself, exactly as the arithmetic mode above.
 std::atomic<int>& osd_depth_setting();
-int& call_osd_slot();                                     // thread-local: the current call's depth, kOsdUnset outside a call
-constexpr int kOsdUnset = -2;
-inline int call_osd_depth() { const int m = call_osd_slot(); return m == kOsdUnset ? osd_depth_setting().load() : m; }
-struct OsdScope {
-    bool owner;
-    OsdScope() : owner(call_osd_slot() == kOsdUnset) { if (owner) call_osd_slot() = osd_depth_setting().load(); }
-    explicit OsdScope(int depth) : owner(call_osd_slot() == kOsdUnset) { if (owner) call_osd_slot() = depth; }
-    ~OsdScope() { if (owner) call_osd_slot() = kOsdUnset; }
-    OsdScope(const OsdScope&) = delete;
-    OsdScope& operator=(const OsdScope&) = delete;
-};
-
-// wspr_set_block_detection(): the process-wide largest block size of the block-detection stage (1 off, 2, 3).  Read ONCE
-// per call, on entry, and handed to the threads a call starts for itself, exactly as the two settings above.
 std::atomic<int>& block_setting();
-int& call_block_slot();                                   // thread-local: the current call's value, 0 outside a call
-inline int call_maxblock() { const int m = call_block_slot(); return m == 0 ? block_setting().load() : m; }
-struct BlockScope {
-    bool owner;
-    BlockScope() : owner(call_block_slot() == 0) { if (owner) call_block_slot() = block_setting().load(); }
-    explicit BlockScope(int maxblock) : owner(call_block_slot() == 0) { if (owner) call_block_slot() = maxblock; }
-    ~BlockScope() { if (owner) call_block_slot() = 0; }
-    BlockScope(const BlockScope&) = delete;
-    BlockScope& operator=(const BlockScope&) = delete;
-};
-
-// wspr_set_spread_estimate(): process-wide, 0 off, 1 on.  Read ONCE per call, on entry, and handed to the threads a call
-// starts for itself, exactly as the settings above.
 std::atomic<int>& spread_setting();
-int& call_spread_slot();                                  // thread-local: the current call's value, -1 outside a call
-inline int call_spread() { const int m = call_spread_slot(); return m < 0 ? spread_setting().load() : m; }
-struct SpreadScope {
-    bool owner;
-    SpreadScope() : owner(call_spread_slot() < 0) { if (owner) call_spread_slot() = spread_setting().load(); }
-    explicit SpreadScope(int on) : owner(call_spread_slot() < 0) { if (owner) call_spread_slot() = on; }
-    ~SpreadScope() { if (owner) call_spread_slot() = -1; }
-    SpreadScope(const SpreadScope&) = delete;
-    SpreadScope& operator=(const SpreadScope&) = delete;
+// A call reads them ONCE, on entry: the outermost entry point of the calling thread holds a CallScope, which takes the
+// snapshot, and everything the call does reads it through the call_*() accessors (outside a call they read the
+// process-wide value).  A thread the call starts for itself (slots, node workers) installs the caller's snapshot with
+// CallScope(settings).
+struct CallSettings {
+    int arith = 0, osd_depth = -1, maxblock = 1, spread = 0;
+    std::shared_ptr<const MessageList> list;
+    static CallSettings snapshot();
+};
+const CallSettings*& call_settings_slot();                // thread-local: the current call's snapshot, null outside a call
+inline CallSettings call_settings() { const CallSettings* s = call_settings_slot(); return s ? *s : CallSettings::snapshot(); }
+inline int call_arith() { const CallSettings* s = call_settings_slot(); return s ? s->arith : arith_setting().load(); }
+inline int call_osd_depth() { const CallSettings* s = call_settings_slot(); return s ? s->osd_depth : osd_depth_setting().load(); }
+inline int call_maxblock() { const CallSettings* s = call_settings_slot(); return s ? s->maxblock : block_setting().load(); }
+inline int call_spread() { const CallSettings* s = call_settings_slot(); return s ? s->spread : spread_setting().load(); }
+inline std::shared_ptr<const MessageList> call_list() {
+    const CallSettings* s = call_settings_slot();
+    return s ? s->list : message_list_setting();
+}
+inline uint64_t call_list_generation() { const auto l = call_list(); return l ? l->generation : 0; }
+struct CallScope {
+    const bool owner;
+    CallSettings mine;
+    CallScope() : owner(!call_settings_slot()) { if (owner) { mine = CallSettings::snapshot(); call_settings_slot() = &mine; } }
+    explicit CallScope(const CallSettings& s) : owner(!call_settings_slot()) { if (owner) { mine = s; call_settings_slot() = &mine; } }
+    ~CallScope() { if (owner) call_settings_slot() = nullptr; }
+    CallScope(const CallScope&) = delete;
+    CallScope& operator=(const CallScope&) = delete;
 };
 // The records wspr_last_spreads() hands back: the calling thread's most recent decode call's, in the layout of that
 // call's `decodes` array.  on = the call ran with the stage on and is of a family that records them.
@@ -215,8 +194,10 @@ public:
     // the wave-parallel search (k6_fano_wave.hip) over host vectors; steps (may be null): expansion steps per vector
     int fano_batch(const unsigned char* symbols, int n, unsigned maxcycles, int* ret, unsigned* cycles,
                    unsigned* metric, unsigned* maxnp, unsigned char* data, unsigned* steps = nullptr);
+    // ... and over vectors already in HBM (vector i at d_symbols + h_offsets[i] * 162; h_symbols: their host copy, if any)
     int fano_resident(const unsigned char* d_symbols, const int* h_offsets, int n, unsigned maxcycles, int* ret,
-                      unsigned* cycles, unsigned char* data);
+                      unsigned* cycles, unsigned char* data, unsigned* metric = nullptr, unsigned* maxnp = nullptr,
+                      unsigned* steps = nullptr, const unsigned char* h_symbols = nullptr);
     // K9 (k9_osd.hip; the definition in kernels/osd.h) over host vectors, and over vectors already in HBM (vector i at
     // d_symbols + h_offsets[i] * 162); results on the host: data n*11, dist, nhard, order
     int osd_batch(const unsigned char* symbols, int n, int depth, unsigned char* data, unsigned* dist, unsigned* nhard,

@@ -12,6 +12,7 @@
 //     for everybody, the remaining 42 steps only for the candidates that need them.
 // The Fano decoder, message unpacking and re-encoding stay on the host (north star).
 #include "wspr_context_impl.h"
+#include "wspr_fano_walk.h"
 
 namespace wspr {
 
@@ -110,15 +111,34 @@ void Context::fetch_candidates(int nseg, std::vector<int>& npk, std::vector<DevC
 // ---------------------------------------------------------------- decoding ---
 namespace {
 
+// the stage whose decode an item carries (an item that is not decoded carries none)
+enum class Stage : unsigned char { None, Ladder, Block2, Block3, List, Osd, kCount };
+inline int block_of(Stage s) { return s == Stage::Block2 ? 2 : s == Stage::Block3 ? 3 : 1; }
+
 struct WaveItem {
     int seg, cand;
     // filled by the GPU wave
     FineState fine;
     bool worth = false, decoded = false, rung0_pending = false;
+    bool gate0 = false;                       // its rung-0 vector passed the sync/rms gate
+    Stage stage = Stage::None;
     int  jitter = 0;
-    unsigned cycles = 0;
+    unsigned cycles = 0;                      // of the Fano search; 0 marks an ordered-statistics decode, 1 a list decode
     unsigned char decdata[11];
+    void decode_by(Stage st, int jit, unsigned cyc, const unsigned char* data11) {
+        decoded = true; stage = st; jitter = jit; cycles = cyc;
+        memcpy(decdata, data11, 11);
+    }
+    void undecode() { decoded = false; stage = Stage::None; }
 };
+
+// the wave's items that were worth a ladder and are not decoded yet (gate0: ... and whose rung-0 vector passed the gate)
+inline std::vector<int> undecoded(const std::vector<WaveItem>& wave, bool gate0 = false) {
+    std::vector<int> todo;
+    for (int i = 0; i < (int)wave.size(); ++i)
+        if (wave[i].worth && !wave[i].decoded && (!gate0 || wave[i].gate0)) todo.push_back(i);
+    return todo;
+}
 
 // CPU time of the calling thread (not wall time: a thread asleep in an event wait costs nothing) added to *acc
 struct CpuSpan {
@@ -201,36 +221,25 @@ std::atomic<int>& arith_setting() {
     static std::atomic<int> v{0};
     return v;
 }
-int& call_arith_slot() {
-    thread_local int m = -1;
-    return m;
-}
-
 std::atomic<int>& osd_depth_setting() {
     static std::atomic<int> v{-1};
     return v;
 }
-int& call_osd_slot() {
-    thread_local int m = kOsdUnset;
-    return m;
-}
-
 std::atomic<int>& block_setting() {
     static std::atomic<int> v{1};
     return v;
 }
-int& call_block_slot() {
-    thread_local int m = 0;
-    return m;
-}
-
 std::atomic<int>& spread_setting() {
     static std::atomic<int> v{0};
     return v;
 }
-int& call_spread_slot() {
-    thread_local int m = -1;
-    return m;
+CallSettings CallSettings::snapshot() {
+    return CallSettings{arith_setting().load(), osd_depth_setting().load(), block_setting().load(), spread_setting().load(),
+                        message_list_setting()};
+}
+const CallSettings*& call_settings_slot() {
+    thread_local const CallSettings* s = nullptr;
+    return s;
 }
 LastSpreads& last_spreads_of_thread() {
     thread_local LastSpreads l;
@@ -293,8 +302,8 @@ int Context::decode_resident(int nseg, int samples, const decoder_options& opt, 
         fano_batch(pend.sym.data(), np, 10000u, ret.data(), cyc.data(), met.data(), mnp.data(), dat.data());
         std::vector<char> dirty(nseg, 0);
         for (int i = 0; i < np; ++i) {
-            c.n_fano++; c.n_cycles += cyc[i];
-            if (ret[i] == 0) dirty[pend.seg[i]] = 1; else c.n_timeout++;
+            c.count_fano(ret[i], cyc[i]);
+            if (ret[i] == 0) dirty[pend.seg[i]] = 1;
         }
         c.t_ms[kTmDeviceFanoTailMs] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_t0).count();
         std::vector<int> redo;
@@ -341,21 +350,14 @@ struct Context::DecodeRun {
         unsigned char sym0[kNSymD];
     };
     std::vector<ItemTrace> wtrace;
-    // wspr_set_osd_depth() of this call (-1: off), and per item of the current wave: its rung-0 vector passed the
-    // sync/rms gate; its decode is the rescue stage's (decided by the "heard before" gate in keep_books())
+    // wspr_set_osd_depth() (-1: off), wspr_set_block_detection() (1: off) and wspr_set_message_list() (null: off) of this
+    // call; which stage decoded an item is WaveItem::stage (an ordered-statistics decode is provisional until the "heard
+    // before" gate in keep_books())
     const int osd_depth = call_osd_depth();
-    std::vector<char> gate0, by_osd;
-    std::atomic<long> n_osd_spots{0};         // candidates the gate let through (bookkeeping runs on the pool's threads)
-    const unsigned char* d_sym0 = nullptr;    // the wave's rung-0 soft symbols in HBM
-    // wspr_set_block_detection() of this call (1: off), and per item of the current wave the block size that decoded it
-    // (0: not this stage)
     const int maxblock = call_maxblock();
-    std::vector<unsigned char> by_block;
-    std::atomic<long> n_block_decodes[2] = {{0}, {0}};   // consumed decodes by block size 2 and 3
-    // wspr_set_message_list() of this call (null: off), and per item of the current wave: its decode is the list stage's
     const std::shared_ptr<const MessageList> list = call_list();
-    std::vector<char> by_list;
-    std::atomic<long> n_list_spots{0};        // consumed decodes of the stage
+    const unsigned char* d_sym0 = nullptr;    // the wave's rung-0 soft symbols in HBM
+    std::atomic<long> n_stage[(int)Stage::kCount] = {};   // consumed decodes of the rescue stages (bookkeeping runs on the pool's threads)
     // wspr_set_spread_estimate() of this call.  keep_books() leaves the wave's jobs here (one per decode that added a
     // spot) with the place of each result among the segment's spots; launch_spreads() queues them ahead of the wave's
     // subtraction, collect_spreads() files the results once the stream has passed them.
@@ -433,10 +435,27 @@ struct Context::DecodeRun {
     bool gated(size_t g) const { return h_sync[g] > minsync2 && h_rms[g] > minrms; }
     // rung r of the rest of the ladder = lag index (jitter + 63) / 3 of the 43-lag block of remaining_rungs()
     int ladder_lag(int r) const { return (c.jitter_ladder[r + 1] + 63) / 3; }
-    static void take_device_result(WaveItem& w, bool decoded, unsigned cycles, const unsigned char* data10) {
-        w.decoded = decoded; w.cycles = cycles;
-        memset(w.decdata, 0, sizeof w.decdata);
-        memcpy(w.decdata, data10, 10);
+    // The walk's attempts where this batch's Fano attempts go: the device search over the vectors in HBM, or the host
+    // pool (all threads from `pool_items` = 256 on) over their copy on the host.
+    void run_walk(FanoWalk& fw, const unsigned char* d_vec, const unsigned char* h_vec, int pool_items) {
+        if (c.dev_fano) {
+            fw.run_device([&](const int* off, int n, int* ret, unsigned* cyc, unsigned char* data10) {
+                ctx.fano_resident(d_vec, off, n, 10000u, ret, cyc, data10);
+            });
+            return;
+        }
+        Pool& fpool = (pool_items >= 256) ? *c.bigpool : *c.pool;
+        fw.run_host([&](int n, const std::function<void(int)>& task) { fpool.run(n, task, 1); },
+                    [&](int off, unsigned* cyc, unsigned char* data11) {
+                        return fano_attempt(h_vec + (size_t)off * kNSymD, cyc, data11);
+                    }, fast != 0);
+    }
+    // The walk's share of n_fano / n_cycles / n_timeout under one of its two rules (FanoWalk::serial, ::as_run)
+    int count_walk(const FanoWalk& fw, bool (FanoWalk::*rule)(int) const) {
+        int n = 0;
+        for (int k = 0; k < (int)fw.att.size(); ++k)
+            if ((fw.*rule)(k)) { c.count_fano(fw.res[k].ret, fw.res[k].cycles); ++n; }
+        return n;
     }
     char* hashtab_of(int s) const { return c.hash_arena + (size_t)s * per_seg; }
     char* loctab_of(int s) const { return c.hash_arena + (size_t)s * per_seg + (size_t)kHashSlots * kHashWidth; }
@@ -651,12 +670,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
         const int* cnt = reinterpret_cast<const int*>(h_down + o_cnt);
         c.t_ms[kTmLagExactEvals] += cnt[0]; c.t_ms[kTmLagFallbacks] += cnt[1]; c.t_ms[kTmLagPruned] += cnt[2];
     }
-    if (list) this->d_sym0 = d_sym0;                           // the list stage matches the rung-0 vectors where they lie
-    if (osd_depth >= 0) {                                      // the rescue stage needs these after the ladder reused the block
-        this->d_sym0 = d_sym0;
-        gate0.resize(nw);
-        for (int i = 0; i < nw; ++i) gate0[i] = gated(i) ? 1 : 0;
-    }
+    this->d_sym0 = d_sym0;                 // the list and the rescue stage read the rung-0 vectors where they lie
 
     if (trace)
         for (int i = 0; i < nw; ++i) {
@@ -670,47 +684,35 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
         }
     // ---- first rung of the jitter ladder -----------------------------------
     const auto t_f0 = std::chrono::steady_clock::now();
+    auto start_item = [&](int i) {                             // what came down for item i; true: its rung-0 vector goes to Fano
+        WaveItem& w = wave[i];
+        w.fine = h_items[i];
+        w.worth = w.fine.sync > minsync1;
+        return w.gate0 = w.worth && gated(i);
+    };
     if (c.dev_fano) {
         // every gated vector of the wave to the device search, straight from the rung-0 symbols in HBM
-        std::vector<int> att;
-        for (int i = 0; i < nw; ++i) {
-            WaveItem& w = wave[i];
-            w.fine = h_items[i];
-            w.worth = w.fine.sync > minsync1;
-            w.decoded = false;
-            w.jitter = 0;
-            w.rung0_pending = false;
-            if (w.worth && gated(i)) att.push_back(i);
-        }
-        const int na = (int)att.size();
-        std::vector<int> ret(na);
-        std::vector<unsigned> cyc(na);
-        std::vector<unsigned char> dat((size_t)na * 10);
-        ctx.fano_resident(d_sym0, att.data(), na, 10000u, ret.data(), cyc.data(), dat.data());
-        for (int k = 0; k < na; ++k) {
-            WaveItem& w = wave[att[k]];
-            take_device_result(w, ret[k] == 0, cyc[k], dat.data() + (size_t)k * 10);
-            c.n_fano++; c.n_cycles += cyc[k]; if (ret[k]) c.n_timeout++;
-        }
+        FanoWalk fw(nw, 1);
+        for (int i = 0; i < nw; ++i)
+            if (start_item(i)) fw.add(i, 0, i);
+        run_walk(fw, d_sym0, nullptr, nw);
+        count_walk(fw, &FanoWalk::serial);                     // one rank: every attempt
+        for (int i = 0; i < nw; ++i)
+            if (fw.at[i] >= 0) wave[i].decode_by(Stage::Ladder, 0, fw.res[fw.at[i]].cycles, fw.res[fw.at[i]].data);
         c.t_ms[kTmDeviceFanoTailMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f0).count();
         return;
     }
     // a candidate that passes the gates but does not decode costs a full time-out here
     // (milliseconds) while a decode costs microseconds: one task per grab, all threads
+    // (the items are filled in by the pool's threads as well, and the grab follows the wave's size: not the walk's loop)
     Pool& pool0 = (nw >= 256) ? *c.bigpool : *c.pool;
     pool0.run(nw, [&](int i) {
+        if (!start_item(i)) return;
         WaveItem& w = wave[i];
-        w.fine = h_items[i];
-        w.worth = w.fine.sync > minsync1;
-        w.decoded = false;
-        w.jitter = 0;
-        if (!w.worth) return;
-        if (gated(i)) {
-            const int nd = fano_attempt(h_sym + (size_t)i * kNSymD, &w.cycles, w.decdata);
-            w.decoded = (nd == 0);
-            w.rung0_pending = (nd != 0) && fast;
-            if (!w.rung0_pending) { c.n_fano++; c.n_cycles += w.cycles; if (nd) c.n_timeout++; }
-        }
+        const int nd = fano_attempt(h_sym + (size_t)i * kNSymD, &w.cycles, w.decdata);
+        if (nd == 0) { w.decoded = true; w.stage = Stage::Ladder; }
+        w.rung0_pending = (nd != 0) && fast;
+        if (!w.rung0_pending) c.count_fano(nd, w.cycles);      // every attempt that ran to a final answer
     }, nw >= 256 ? 1 : 0);
     c.t_ms[kTmHostFanoMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f0).count();
 
@@ -721,13 +723,9 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
 
 // Remaining rungs of the jitter ladder, only for candidates that still need them
 void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
-    const int nw = (int)wave.size();
     const float* wi = c.iqI.as<float>();
     const float* wq = c.iqQ.as<float>();
-    std::vector<int> again;
-    if (njit_rest > 0)
-        for (int i = 0; i < nw; ++i)
-            if (wave[i].worth && !wave[i].decoded) again.push_back(i);
+    const std::vector<int> again = njit_rest > 0 ? undecoded(wave) : std::vector<int>();
     if (!again.empty()) {
         const int na = (int)again.size();
         FineState* h2 = static_cast<FineState*>(c.h_misc.need((size_t)na * sizeof(FineState)));
@@ -756,98 +754,29 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
             h_rms = reinterpret_cast<float*>(h_blk + o_rms);
             h_sym = reinterpret_cast<unsigned char*>(h_blk + o_sym);
         }
-        // trace: the serial walk stops at the first success, rung `lastr` of the rest (or walks all of them)
-        auto trace_ladder = [&](int a, int lastr) {
-            if (!trace) return;
-            ItemTrace& t = wtrace[again[a]];
-            t.attempts = 1 + (lastr + 1);
-            for (int r = 0; r <= lastr; ++r) {
-                const int g = a * kMaxLags + ladder_lag(r);
-                if (gated(g)) t.fano_calls++;
-            }
-        };
-        if (c.dev_fano) {
-            // every gated (candidate, rung) vector to the device search; the ladder keeps the first success in
-            // rung order, so all are run and the pick is made afterwards (a candidate that decodes on an early
-            // rung wastes its later ones: few do)
-            const auto t_d0 = std::chrono::steady_clock::now();
-            std::vector<int> off, who;
-            for (int a = 0; a < na; ++a)
-                for (int r = 0; r < njit_rest; ++r) {
-                    const int g = a * kMaxLags + ladder_lag(r);
-                    if (gated(g)) { off.push_back(g); who.push_back(a * njit_rest + r); }
-                }
-            const int nv = (int)off.size();
-            std::vector<int> ret(nv);
-            std::vector<unsigned> cyc(nv);
-            std::vector<unsigned char> dat((size_t)nv * 10);
-            ctx.fano_resident(d_sym, off.data(), nv, 10000u, ret.data(), cyc.data(), dat.data());
-            std::vector<int> first(na, njit_rest), at(na, -1);
-            for (int k = 0; k < nv; ++k) {
-                const int a = who[k] / njit_rest, r = who[k] % njit_rest;
-                if (r <= first[a]) { c.n_fano++; c.n_cycles += cyc[k]; if (ret[k]) c.n_timeout++; }   // what the serial walk would have run
-                if (ret[k] == 0 && r < first[a]) { first[a] = r; at[a] = k; }
-            }
-            for (int a = 0; a < na; ++a) {
-                trace_ladder(a, at[a] >= 0 ? first[a] : njit_rest - 1);
-                if (at[a] < 0) continue;
-                WaveItem& w = wave[again[a]];
-                w.jitter = c.jitter_ladder[first[a] + 1];
-                take_device_result(w, true, cyc[at[a]], dat.data() + (size_t)at[a] * 10);
-            }
-            c.t_ms[kTmDeviceFanoTailMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_d0).count();
-            return;
-        }
+        // every gated (candidate, rung) vector is searched and the ladder keeps the FIRST success in rung order (on the
+        // device a candidate that decodes on an early rung wastes its later ones: few do)
         const auto t_f1 = std::chrono::steady_clock::now();
-        // every (candidate, rung) Fano attempt is independent; the ladder keeps the
-        // FIRST success in rung order, so run them all and pick afterwards
-        struct Attempt { int ok; int pending; unsigned cycles; unsigned char data[11]; };
-        std::vector<Attempt> att((size_t)na * njit_rest);
-        std::vector<std::atomic<int>> first(na);
-        for (auto& f : first) f.store(njit_rest);
-        Pool& fpool = (na * njit_rest >= 256) ? *c.bigpool : *c.pool;
-        // rung-major order and one task per grab: a time-out costs ~810 000 decoder cycles
-        // (milliseconds) while a success costs microseconds, so costs are heavy-tailed; low
-        // rungs finish first and cancel the higher rungs of the same candidate
-        fpool.run(na * njit_rest, [&](int task) {
-            const int r = task / na, a = task % na;
-            const int idx = a * njit_rest + r;
-            Attempt& at = att[idx];
-            at.ok = 0;
-            at.pending = 0;
-            if (r > first[a].load()) return;           // an earlier rung already decoded
-            const size_t g = (size_t)a * kMaxLags + (size_t)ladder_lag(r);
-            if (!gated(g)) return;
-            const int nd = fano_attempt(h_sym + g * kNSymD, &at.cycles, at.data);
-            at.pending = (nd != 0) && fast;
-            if (!at.pending) { c.n_fano++; c.n_cycles += at.cycles; if (nd) c.n_timeout++; }
-            if (nd == 0) {
-                at.ok = 1;
-                int cur = first[a].load();
-                while (r < cur && !first[a].compare_exchange_weak(cur, r)) {}
+        FanoWalk fw(na, njit_rest);
+        for (int a = 0; a < na; ++a)
+            for (int r = 0; r < njit_rest; ++r) {
+                const int g = a * kMaxLags + ladder_lag(r);
+                if (gated(g)) fw.add(a, r, g);
             }
-        }, 1);
-        if (fast)      // unfinished attempts on rungs BEFORE the accepted one decide nothing yet
-            for (int a = 0; a < na; ++a) {
-                const int rmax = std::min(first[a].load(), njit_rest);
-                for (int r = 0; r < rmax; ++r)
-                    if (att[(size_t)a * njit_rest + r].pending) {
-                        const size_t g = (size_t)a * kMaxLags + (size_t)ladder_lag(r);
-                        pend.add(wave[again[a]].seg, h_sym + g * kNSymD);
-                    }
-            }
+        run_walk(fw, d_sym, h_sym, na * njit_rest);
+        // device: what the serial walk would have run; host pool: every attempt that ran to a final answer
+        count_walk(fw, c.dev_fano ? &FanoWalk::serial : &FanoWalk::as_run);
+        for (int k = 0; k < (int)fw.att.size(); ++k)
+            if (fw.left_pending(k)) pend.add(wave[again[fw.att[k].a]].seg, h_sym + (size_t)fw.att[k].off * kNSymD);
         for (int a = 0; a < na; ++a) {
-            const int r = first[a].load();
-            trace_ladder(a, (r < njit_rest && att[(size_t)a * njit_rest + r].ok) ? r : njit_rest - 1);
-            if (r < njit_rest && att[(size_t)a * njit_rest + r].ok) {
-                WaveItem& w = wave[again[a]];
-                w.decoded = true;
-                w.jitter = c.jitter_ladder[r + 1];
-                w.cycles = att[(size_t)a * njit_rest + r].cycles;
-                memcpy(w.decdata, att[(size_t)a * njit_rest + r].data, 11);
-            }
+            // trace: the serial walk stops at the first success (or walks all the rungs)
+            if (trace) { wtrace[again[a]].attempts = 1 + fw.walked(a); wtrace[again[a]].fano_calls += fw.calls[a]; }
+            if (fw.at[a] < 0) continue;
+            const FanoWalk::Result& r = fw.res[fw.at[a]];
+            wave[again[a]].decode_by(Stage::Ladder, c.jitter_ladder[fw.win[a] + 1], r.cycles, r.data);
         }
-        c.t_ms[kTmHostFanoMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f1).count();
+        c.t_ms[c.dev_fano ? kTmDeviceFanoTailMs : kTmHostFanoMs] +=
+            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f1).count();
     }
 }
 
@@ -858,11 +787,7 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
 // in (B, rung) order wins.  K10 forms all the vectors of a chunk of candidates at once, every gated one is searched (host
 // pool or K6w, as the ladder) and the pick is made afterwards.  A success is a decode like any other.
 void Context::DecodeRun::block_rescue(std::vector<WaveItem>& wave) {
-    const int nw = (int)wave.size();
-    by_block.assign(nw, 0);
-    std::vector<int> todo;
-    for (int i = 0; i < nw; ++i)
-        if (wave[i].worth && !wave[i].decoded) todo.push_back(i);
+    const std::vector<int> todo = undecoded(wave);
     if (todo.empty()) return;
     const auto t0 = std::chrono::steady_clock::now();
     const int nr = opt.quickmode ? 1 : kMaxLags, nb = maxblock - 1;
@@ -882,59 +807,21 @@ void Context::DecodeRun::block_rescue(std::vector<WaveItem>& wave) {
         if (!c.dev_fano) sym.resize((size_t)nh * 3 * kNSymD);
         const unsigned char* d_vec = nullptr;
         ctx.block_resident(hyps.data(), nh, samples, c.dev_fano ? nullptr : sym.data(), rms.data(), sy.data(), &d_vec);
-        // attempts in the walk's order per candidate: B = 2 .. maxblock, then rung; `off` = the vector's index among the 3 nh
-        std::vector<int> off, who;
+        // attempts in the walk's order per candidate: B = 2 .. maxblock, then rung; the vector's index among the 3 nh
+        FanoWalk fw(na, nb * nr);
         for (int a = 0; a < na; ++a)
             for (int b = 0; b < nb; ++b)
                 for (int r = 0; r < nr; ++r) {
                     const size_t h = (size_t)a * nr + r;
-                    if (sy[h] > minsync2 && rms[h * 3 + b + 1] > minrms) { off.push_back((int)(h * 3 + b + 1)); who.push_back((a * nb + b) * nr + r); }
+                    if (sy[h] > minsync2 && rms[h * 3 + b + 1] > minrms) fw.add(a, b * nr + r, (int)(h * 3 + b + 1));
                 }
-        const int nv = (int)off.size(), per = nb * nr;
-        std::vector<int> ret(nv, -1);
-        std::vector<unsigned> cyc(nv, 0);
-        std::vector<unsigned char> dat((size_t)nv * 11, 0);
-        if (c.dev_fano) {
-            std::vector<unsigned char> d10((size_t)nv * 10);
-            ctx.fano_resident(d_vec, off.data(), nv, 10000u, ret.data(), cyc.data(), d10.data());
-            for (int k = 0; k < nv; ++k) memcpy(dat.data() + (size_t)k * 11, d10.data() + (size_t)k * 10, 10);
-        } else {
-            // attempt-major order and one task per grab, as the ladder: early attempts finish first and cancel the later
-            // ones of the same candidate
-            std::vector<std::atomic<int>> first(na);
-            for (auto& f : first) f.store(per);
-            std::vector<int> order(nv);
-            for (int k = 0; k < nv; ++k) order[k] = k;
-            std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return who[x] % per < who[y] % per; });
-            Pool& fpool = (nv >= 256) ? *c.bigpool : *c.pool;
-            fpool.run(nv, [&](int task) {
-                const int k = order[task], a = who[k] / per, q = who[k] % per;
-                if (q > first[a].load()) return;                // an earlier attempt already decoded
-                ret[k] = fano_attempt(sym.data() + (size_t)off[k] * kNSymD, &cyc[k], dat.data() + (size_t)k * 11);
-                if (ret[k] == 0) {
-                    int cur = first[a].load();
-                    while (q < cur && !first[a].compare_exchange_weak(cur, q)) {}
-                }
-            }, 1);
-        }
-        std::vector<int> first(na, per), at(na, -1);
-        for (int k = 0; k < nv; ++k) {
-            const int a = who[k] / per, q = who[k] % per;
-            if (ret[k] == 0 && q < first[a]) { first[a] = q; at[a] = k; }
-        }
-        for (int k = 0; k < nv; ++k) {                         // what the serial walk would have run
-            const int a = who[k] / per, q = who[k] % per;
-            if (q > first[a]) continue;
-            c.n_fano++; c.n_cycles += cyc[k]; if (ret[k]) c.n_timeout++;
-            c.t_ms[kTmBlockVectors] += 1.0;
-        }
+        run_walk(fw, d_vec, sym.data(), (int)fw.att.size());
+        c.t_ms[kTmBlockVectors] += count_walk(fw, &FanoWalk::serial);   // what the serial walk would have run
         for (int a = 0; a < na; ++a) {
-            if (at[a] < 0) continue;
-            const int i = todo[lo + a], b = first[a] / nr, r = first[a] % nr;
-            WaveItem& w = wave[i];
-            by_block[i] = (unsigned char)(b + 2);
-            w.decoded = true; w.jitter = c.jitter_ladder[r]; w.cycles = cyc[at[a]];
-            memcpy(w.decdata, dat.data() + (size_t)at[a] * 11, 11);
+            if (fw.at[a] < 0) continue;
+            const int b = fw.win[a] / nr, r = fw.win[a] % nr;
+            const FanoWalk::Result& won = fw.res[fw.at[a]];
+            wave[todo[lo + a]].decode_by(b == 0 ? Stage::Block2 : Stage::Block3, c.jitter_ladder[r], won.cycles, won.data);
         }
     }
     c.t_ms[kTmBlockMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -946,11 +833,7 @@ void Context::DecodeRun::block_rescue(std::vector<WaveItem>& wave) {
 // once and without a hash look-up.  An accepted candidate takes the entry's decdata and is a decode like any other;
 // cycles == 1 marks it (Fano: >= 81, the ordered-statistics stage: 0).
 void Context::DecodeRun::list_rescue(std::vector<WaveItem>& wave) {
-    const int nw = (int)wave.size();
-    by_list.assign(nw, 0);
-    std::vector<int> att;
-    for (int i = 0; i < nw; ++i)
-        if (wave[i].worth && !wave[i].decoded) att.push_back(i);
+    const std::vector<int> att = undecoded(wave);
     if (att.empty()) return;
     const auto t0 = std::chrono::steady_clock::now();
     const int na = (int)att.size();
@@ -959,10 +842,7 @@ void Context::DecodeRun::list_rescue(std::vector<WaveItem>& wave) {
     for (int k = 0; k < na; ++k) {
         const wspr_list_match& r = res[k];
         if (r.index < 0 || r.index >= list->n || !listmatch::gate(r.score, r.v2, list->zmin16)) continue;
-        WaveItem& w = wave[att[k]];
-        by_list[att[k]] = 1;
-        w.decoded = true; w.jitter = 0; w.cycles = 1;
-        memcpy(w.decdata, list->decdata.data() + (size_t)r.index * 11, 11);
+        wave[att[k]].decode_by(Stage::List, 0, 1, list->decdata.data() + (size_t)r.index * 11);
     }
     c.t_ms[kTmListMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c.t_ms[kTmListVectors] += (double)na;
@@ -974,23 +854,14 @@ void Context::DecodeRun::list_rescue(std::vector<WaveItem>& wave) {
 // counts as a decode only if keep_books() finds its callsign in the hash memory (osd_accept()).  cycles == 0 marks it:
 // the Fano search never reports fewer than 81.
 void Context::DecodeRun::osd_rescue(std::vector<WaveItem>& wave) {
-    const int nw = (int)wave.size();
-    by_osd.assign(nw, 0);
-    std::vector<int> att;
-    for (int i = 0; i < nw; ++i)
-        if (wave[i].worth && !wave[i].decoded && gate0[i]) att.push_back(i);
+    const std::vector<int> att = undecoded(wave, true);
     if (att.empty()) return;
     const auto t0 = std::chrono::steady_clock::now();
     const int na = (int)att.size();
     std::vector<unsigned char> dat((size_t)na * 11);
     std::vector<unsigned> dist(na), nhard(na), order(na);
     ctx.osd_resident(d_sym0, att.data(), na, osd_depth, dat.data(), dist.data(), nhard.data(), order.data());
-    for (int k = 0; k < na; ++k) {
-        WaveItem& w = wave[att[k]];
-        by_osd[att[k]] = 1;
-        w.decoded = true; w.jitter = 0; w.cycles = 0;
-        memcpy(w.decdata, dat.data() + (size_t)k * 11, 11);
-    }
+    for (int k = 0; k < na; ++k) wave[att[k]].decode_by(Stage::Osd, 0, 0, dat.data() + (size_t)k * 11);
     c.t_ms[kTmOsdMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c.t_ms[kTmOsdVectors] += (double)na;
 }
@@ -1027,10 +898,7 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
         HashTable& tab = shared ? static_cast<HashTable&>(*shared) : (persist ? static_cast<HashTable&>(flat) : static_cast<HashTable&>(bk.hash));
         // an ordered-statistics decode counts only for a call heard before; decided before anything is stored or traced
         // (the look-up is logged like a type-3 look-up, so a batch with usehashtable orders it)
-        if (osd_depth >= 0 && by_osd[i] && w.worth && w.decoded) {
-            if (osd_accept(w.decdata, tab)) n_osd_spots++;
-            else w.decoded = false;
-        }
+        if (w.stage == Stage::Osd && !osd_accept(w.decdata, tab)) w.undecode();
         DevCand& cd = cand[(size_t)s * kMaxCand + w.cand];
         cd.freq = w.fine.freq; cd.shift = w.fine.shift; cd.drift = w.fine.drift; cd.sync = w.fine.sync;
         wspr_cand_trace* tc = nullptr;
@@ -1046,13 +914,12 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
             if (t.attempts > 0) { tc->first_sync = t.sync0; tc->first_rms = t.rms0; memcpy(tc->first_symbols, t.sym0, kNSymD); }
             if (w.worth && w.decoded) {
                 tc->decoded = 1; tc->jitter = w.jitter; tc->cycles = w.cycles;
-                tc->block = (maxblock > 1 && by_block[i]) ? by_block[i] : 1;
+                tc->block = block_of(w.stage);
                 memcpy(tc->decdata, w.decdata, 11);
             }
         }
         if (!(w.worth && w.decoded)) continue;
-        if (maxblock > 1 && by_block[i]) n_block_decodes[by_block[i] - 2]++;
-        if (list && by_list[i]) n_list_spots++;
+        if (w.stage != Stage::Ladder) n_stage[(int)w.stage]++;     // (the ladder's own decodes are not counted: no shared write)
 
         signed char message[12] = {0};
         for (int k = 0; k < 11; ++k) message[k] = (signed char)w.decdata[k];
@@ -1301,10 +1168,10 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
         }
     }
     { CpuSpan sp(&d->t_ms[kTmCpuMsFinish]); run.finish(active0, n_results); }
-    d->t_ms[kTmOsdSpots] += (double)run.n_osd_spots.load();
-    d->t_ms[kTmListSpots] += (double)run.n_list_spots.load();
-    d->t_ms[kTmBlock2Decodes] += (double)run.n_block_decodes[0].load();
-    d->t_ms[kTmBlock3Decodes] += (double)run.n_block_decodes[1].load();
+    d->t_ms[kTmOsdSpots] += (double)run.n_stage[(int)Stage::Osd].load();
+    d->t_ms[kTmListSpots] += (double)run.n_stage[(int)Stage::List].load();
+    d->t_ms[kTmBlock2Decodes] += (double)run.n_stage[(int)Stage::Block2].load();
+    d->t_ms[kTmBlock3Decodes] += (double)run.n_stage[(int)Stage::Block3].load();
     guard.armed = false;
     return 0;
 }
@@ -1481,73 +1348,91 @@ int Context::bench_decimate(const void* d_raw, size_t bytes_per_seg, int nseg, f
 }
 #endif  // WSPR_LAB
 
-// Device Fano search over n host vectors: interleaved soft symbols in, results out.  The wave-parallel
-// kernel reports -2 for a vector whose pending-visit store overflowed (not seen in tests; the serial host
-// decoder takes those).
-int Context::fano_batch(const unsigned char* symbols, int n, unsigned maxcycles, int* ret, unsigned* cycles,
-                        unsigned* metric, unsigned* maxnp, unsigned char* data, unsigned* steps) {
+// ---- resident launches: K6w, K9 and K14 over soft-symbol vectors in HBM, results on the host ----------------------
+// Vector i of a launch is the 162 soft symbols at d_symbols + offsets[i] * 162, transmission order.
+// The offset list of a launch: host -> pinned -> device, queued on the stream.
+static const int* stage_offsets(Context::Impl& c, const int* h_offsets, int n) {
+    int* h_off = static_cast<int*>(c.h_misc.need((size_t)n * 4));
+    memcpy(h_off, h_offsets, (size_t)n * 4);
+    int* doff = static_cast<int*>(c.fz_off.need((size_t)n * 4));
+    upload(doff, h_off, (size_t)n * 4, c.stream);
+    return doff;
+}
+// n host vectors to the device, vector i at offset i (`off`)
+static const unsigned char* stage_vectors(Context::Impl& c, const unsigned char* symbols, int n, std::vector<int>& off) {
+    unsigned char* dsym = static_cast<unsigned char*>(c.fz_sym.need((size_t)n * kNSymD));
+    upload(dsym, symbols, (size_t)n * kNSymD, c.stream);
+    off.resize(n);
+    for (int i = 0; i < n; ++i) off[i] = i;
+    return dsym;
+}
+
+// The wave-parallel search (K6w).  metric / maxnp (both or neither) and steps are optional outputs.  The kernel reports -2
+// for a vector whose pending-visit store overflowed (not seen in tests); the serial host decoder takes those: over
+// h_symbols (the vectors' host copy, vector i at i * 162) on the pool, else one by one after fetching the vector.
+int Context::fano_resident(const unsigned char* d_symbols, const int* h_offsets, int n, unsigned maxcycles, int* ret,
+                           unsigned* cycles, unsigned char* data, unsigned* metric, unsigned* maxnp, unsigned* steps,
+                           const unsigned char* h_symbols) {
     Impl& c = *d;
     if (n <= 0) return 0;
-    int* h_off = static_cast<int*>(c.h_misc.need((size_t)n * 4));
-    for (int i = 0; i < n; ++i) h_off[i] = i;
-    unsigned char* dsym = static_cast<unsigned char*>(c.fz_sym.need((size_t)n * kNSymD));
-    int* doff = static_cast<int*>(c.fz_off.need((size_t)n * 4));
+    const int* doff = stage_offsets(c, h_offsets, n);
     int* dret = static_cast<int*>(c.fz_ret.need((size_t)n * 4));
     unsigned* dcyc = static_cast<unsigned*>(c.fz_cyc.need((size_t)n * 4));
-    unsigned* dmet = static_cast<unsigned*>(c.fz_met.need((size_t)n * 4));
-    unsigned* dmax = static_cast<unsigned*>(c.fz_max.need((size_t)n * 4));
     unsigned char* ddat = static_cast<unsigned char*>(c.fz_dat.need((size_t)n * 10));
+    unsigned* dmet = metric ? static_cast<unsigned*>(c.fz_met.need((size_t)n * 4)) : nullptr;
+    unsigned* dmax = metric ? static_cast<unsigned*>(c.fz_max.need((size_t)n * 4)) : nullptr;
     unsigned* dsteps = steps ? static_cast<unsigned*>(c.fz_steps.need((size_t)n * 4)) : nullptr;
-    upload(dsym, symbols, (size_t)n * kNSymD, c.stream);
-    upload(doff, h_off, (size_t)n * 4, c.stream);
-    launch_fano_wave(dsym, doff, n, c.t_metric0.as<short>(), maxcycles, dret, dcyc, dmet, dmax, ddat, dsteps,
+    launch_fano_wave(d_symbols, doff, n, c.t_metric0.as<short>(), maxcycles, dret, dcyc, dmet, dmax, ddat, dsteps,
                      static_cast<uint32_t*>(c.fz_pool.need(fano_wave_scratch_words(n) * 4)), c.stream);
-    char* hz = static_cast<char*>(c.h_fz.need((size_t)n * 30));
-    HIP_OK(hipMemcpyAsync(hz, dret, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpyAsync(hz + (size_t)n * 4, dcyc, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpyAsync(hz + (size_t)n * 8, dmet, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpyAsync(hz + (size_t)n * 12, dmax, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpyAsync(hz + (size_t)n * 16, ddat, (size_t)n * 10, hipMemcpyDeviceToHost, c.stream));
-    if (steps) HIP_OK(hipMemcpyAsync(hz + (size_t)n * 26, dsteps, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
+    // through pinned memory (a copy into pageable memory would make the runtime wait for the search itself, on a CPU)
+    char* hz = static_cast<char*>(c.h_fz.need((size_t)n * (18 + (metric ? 8 : 0) + (steps ? 4 : 0))));
+    struct Part { void* host; const void* dev; size_t each; } parts[] = {{ret, dret, 4},     {cycles, dcyc, 4}, {data, ddat, 10},
+                                                                        {metric, dmet, 4}, {maxnp, dmax, 4},  {steps, dsteps, 4}};
+    size_t at = 0;
+    for (const Part& p : parts)
+        if (p.dev) { HIP_OK(hipMemcpyAsync(hz + at, p.dev, (size_t)n * p.each, hipMemcpyDeviceToHost, c.stream)); at += (size_t)n * p.each; }
     sync();
-    memcpy(ret, hz, (size_t)n * 4);
-    memcpy(cycles, hz + (size_t)n * 4, (size_t)n * 4);
-    memcpy(metric, hz + (size_t)n * 8, (size_t)n * 4);
-    memcpy(maxnp, hz + (size_t)n * 12, (size_t)n * 4);
-    memcpy(data, hz + (size_t)n * 16, (size_t)n * 10);
-    if (steps) memcpy(steps, hz + (size_t)n * 26, (size_t)n * 4);
-    {
-        std::vector<int> redo;
-        for (int i = 0; i < n; ++i) if (ret[i] == -2) redo.push_back(i);
-        if (!redo.empty()) {
-            const FanoMetrics& met = default_metrics();
-            c.bigpool->run((int)redo.size(), [&](int k) {
-                const int i = redo[k];
-                unsigned char sym[kNSymD], out11[11] = {0};
-                memcpy(sym, symbols + (size_t)i * kNSymD, kNSymD);
-                deinterleave162(sym);
-                ret[i] = fano_decode(&metric[i], &cycles[i], &maxnp[i], out11, sym, kNBits, met.tab, 60, maxcycles);
-                memcpy(data + (size_t)i * 10, out11, 10);
-            }, 1);
-        }
-    }
+    at = 0;
+    for (const Part& p : parts)
+        if (p.dev) { memcpy(p.host, hz + at, (size_t)n * p.each); at += (size_t)n * p.each; }
+    std::vector<int> redo;
+    for (int i = 0; i < n; ++i) if (ret[i] == -2) redo.push_back(i);
+    if (redo.empty()) return 0;
+    const FanoMetrics& met = default_metrics();
+    auto serial = [&](int k) {
+        const int i = redo[k];
+        unsigned char sym[kNSymD], out11[11] = {0};
+        if (h_symbols) memcpy(sym, h_symbols + (size_t)i * kNSymD, kNSymD);
+        else HIP_OK(hipMemcpy(sym, d_symbols + (size_t)h_offsets[i] * kNSymD, kNSymD, hipMemcpyDeviceToHost));
+        deinterleave162(sym);
+        unsigned m, np;
+        ret[i] = fano_decode(metric ? &metric[i] : &m, &cycles[i], maxnp ? &maxnp[i] : &np, out11, sym, kNBits, met.tab, 60, maxcycles);
+        memcpy(data + (size_t)i * 10, out11, 10);
+    };
+    if (h_symbols) c.bigpool->run((int)redo.size(), serial, 1);
+    else for (int k = 0; k < (int)redo.size(); ++k) serial(k);
     return 0;
 }
 
-// K9 over vectors that are already in HBM (the decode loop's rescue stage): vector i is the 162 soft symbols at
-// d_symbols + h_offsets[i] * 162, transmission order.  Results on the host.
+// K6w over n host vectors (wspr_fano_batch_device_wave, and the tail of the budget split)
+int Context::fano_batch(const unsigned char* symbols, int n, unsigned maxcycles, int* ret, unsigned* cycles,
+                        unsigned* metric, unsigned* maxnp, unsigned char* data, unsigned* steps) {
+    if (n <= 0) return 0;
+    std::vector<int> off;
+    const unsigned char* dsym = stage_vectors(*d, symbols, n, off);
+    return fano_resident(dsym, off.data(), n, maxcycles, ret, cycles, data, metric, maxnp, steps, symbols);
+}
+
+// K9 (the decode loop's rescue stage)
 int Context::osd_resident(const unsigned char* d_symbols, const int* h_offsets, int n, int depth, unsigned char* data,
                           unsigned* dist, unsigned* nhard, unsigned* order) {
     Impl& c = *d;
     if (n <= 0) return 0;
-    int* h_off = static_cast<int*>(c.h_misc.need((size_t)n * 4));
-    memcpy(h_off, h_offsets, (size_t)n * 4);
-    int* doff = static_cast<int*>(c.fz_off.need((size_t)n * 4));
+    const int* doff = stage_offsets(c, h_offsets, n);
     // one result block [dist | nhard | order | data]: one copy down
     const size_t o_data = (size_t)n * 12, blk = o_data + (size_t)n * 11;
     char* dout = static_cast<char*>(c.osd_out.need(blk));
     char* hout = static_cast<char*>(c.h_osd.need(blk));
-    upload(doff, h_off, (size_t)n * 4, c.stream);
     launch_osd(d_symbols, doff, n, depth, c.t_osdgen.as<uint32_t>(), reinterpret_cast<unsigned char*>(dout + o_data),
                reinterpret_cast<unsigned*>(dout), reinterpret_cast<unsigned*>(dout + (size_t)n * 4),
                reinterpret_cast<unsigned*>(dout + (size_t)n * 8), c.stream);
@@ -1561,9 +1446,8 @@ int Context::osd_resident(const unsigned char* d_symbols, const int* h_offsets, 
     return 0;
 }
 
-// K14 over vectors that are already in HBM (the decode loop's list stage): vector i is the 162 soft symbols at
-// d_symbols + h_offsets[i] * 162, transmission order, against `list`.  The list's table goes up on first use and stays
-// until a call brings another list (its generation tells).  Results on the host.
+// K14 (the decode loop's list stage) against `list`.  The list's table goes up on first use and stays until a call brings
+// another list (its generation tells).
 int Context::list_resident(const unsigned char* d_symbols, const int* h_offsets, int n, const MessageList& list,
                            wspr_list_match* out) {
     static_assert(sizeof(ListMatch) == sizeof(wspr_list_match), "public and internal result layouts differ");
@@ -1583,13 +1467,10 @@ int Context::list_resident(const unsigned char* d_symbols, const int* h_offsets,
         c.list_gen = list.generation;
     }
     const char* t = c.t_list.as<char>();
-    int* h_off = static_cast<int*>(c.h_misc.need((size_t)n * 4));
-    memcpy(h_off, h_offsets, (size_t)n * 4);
-    int* doff = static_cast<int*>(c.fz_off.need((size_t)n * 4));
+    const int* doff = stage_offsets(c, h_offsets, n);
     const size_t blk = (size_t)n * sizeof(ListMatch);
     ListMatch* dout = static_cast<ListMatch*>(c.list_out.need(blk));
     char* hout = static_cast<char*>(c.h_list.need(blk));
-    upload(doff, h_off, (size_t)n * 4, c.stream);
     launch_list_match(d_symbols, doff, n, reinterpret_cast<const int*>(t), reinterpret_cast<const int*>(t + tab_bytes), list.n,
                       dout, c.stream);
     HIP_OK(hipGetLastError());
@@ -1601,62 +1482,19 @@ int Context::list_resident(const unsigned char* d_symbols, const int* h_offsets,
 
 // K14 over n host vectors (wspr_list_match_batch_device)
 int Context::list_batch(const unsigned char* symbols, int n, const MessageList& list, wspr_list_match* out) {
-    Impl& c = *d;
     if (n <= 0) return 0;
-    unsigned char* dsym = static_cast<unsigned char*>(c.fz_sym.need((size_t)n * kNSymD));
-    upload(dsym, symbols, (size_t)n * kNSymD, c.stream);
-    std::vector<int> off(n);
-    for (int i = 0; i < n; ++i) off[i] = i;
+    std::vector<int> off;
+    const unsigned char* dsym = stage_vectors(*d, symbols, n, off);
     return list_resident(dsym, off.data(), n, list, out);
 }
 
 // K9 over n host vectors (wspr_osd_batch_device)
 int Context::osd_batch(const unsigned char* symbols, int n, int depth, unsigned char* data, unsigned* dist,
                        unsigned* nhard, unsigned* order) {
-    Impl& c = *d;
     if (n <= 0) return 0;
-    unsigned char* dsym = static_cast<unsigned char*>(c.fz_sym.need((size_t)n * kNSymD));
-    upload(dsym, symbols, (size_t)n * kNSymD, c.stream);
-    std::vector<int> off(n);
-    for (int i = 0; i < n; ++i) off[i] = i;
+    std::vector<int> off;
+    const unsigned char* dsym = stage_vectors(*d, symbols, n, off);
     return osd_resident(dsym, off.data(), n, depth, data, dist, nhard, order);
-}
-
-// Device Fano search over vectors that are already in HBM: attempt i is the 162 soft symbols at
-// d_symbols + h_offsets[i] * 162 (transmission order).  Results on the host; a vector whose pending-visit
-// store overflowed (-2) is fetched and decoded by the serial host routine.
-int Context::fano_resident(const unsigned char* d_symbols, const int* h_offsets, int n, unsigned maxcycles, int* ret,
-                           unsigned* cycles, unsigned char* data) {
-    Impl& c = *d;
-    if (n <= 0) return 0;
-    int* h_off = static_cast<int*>(c.h_misc.need((size_t)n * 4));
-    memcpy(h_off, h_offsets, (size_t)n * 4);
-    int* doff = static_cast<int*>(c.fz_off.need((size_t)n * 4));
-    int* dret = static_cast<int*>(c.fz_ret.need((size_t)n * 4));
-    unsigned* dcyc = static_cast<unsigned*>(c.fz_cyc.need((size_t)n * 4));
-    unsigned char* ddat = static_cast<unsigned char*>(c.fz_dat.need((size_t)n * 10));
-    upload(doff, h_off, (size_t)n * 4, c.stream);
-    launch_fano_wave(d_symbols, doff, n, c.t_metric0.as<short>(), maxcycles, dret, dcyc, nullptr, nullptr, ddat, nullptr,
-                     static_cast<uint32_t*>(c.fz_pool.need(fano_wave_scratch_words(n) * 4)), c.stream);
-    char* hz = static_cast<char*>(c.h_fz.need((size_t)n * 18));
-    HIP_OK(hipMemcpyAsync(hz, dret, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpyAsync(hz + (size_t)n * 4, dcyc, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpyAsync(hz + (size_t)n * 8, ddat, (size_t)n * 10, hipMemcpyDeviceToHost, c.stream));
-    sync();
-    memcpy(ret, hz, (size_t)n * 4);
-    memcpy(cycles, hz + (size_t)n * 4, (size_t)n * 4);
-    memcpy(data, hz + (size_t)n * 8, (size_t)n * 10);
-    const FanoMetrics& met = default_metrics();
-    for (int i = 0; i < n; ++i) {
-        if (ret[i] != -2) continue;
-        unsigned char sym[kNSymD], out11[11] = {0};
-        HIP_OK(hipMemcpy(sym, d_symbols + (size_t)h_offsets[i] * kNSymD, kNSymD, hipMemcpyDeviceToHost));
-        deinterleave162(sym);
-        unsigned metric, maxnp;
-        ret[i] = fano_decode(&metric, &cycles[i], &maxnp, out11, sym, kNBits, met.tab, 60, maxcycles);
-        memcpy(data + (size_t)i * 10, out11, 10);
-    }
-    return 0;
 }
 
 }  // namespace wspr

@@ -1,6 +1,7 @@
 // Driver of tests/test_gpu_fine.py: runs the fine search of a case file -- mode 0 (lag scan), mode 1 (frequency scan) with
 // the first rung, and the 43 lags of the jitter ladder -- through the PRODUCTION launchers, in the order of
-// DecodeRun::refine_and_first_rung() / remaining_rungs() (wspr_pipeline.hip), and dumps every buffer.  It judges nothing:
+// DecodeRun::refine_and_first_rung() / remaining_rungs() (wspr_pipeline.hip; what they do with the vectors afterwards is
+// the Fano walk of host/wspr_fano_walk.h, not run here), and dumps every buffer.  It judges nothing:
 // the assertions live in the test (tests/fine_lib.py describes both file formats).  Exit status: 0, 1 = a HIP error
 // (nothing is started after one), 2 = the case file is unusable.  Includes the kernel file itself.
 // hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-fast-math -I rtlsdr-wsprd_amd/csrc/kernels tools/fine_check.hip -o tools/fine_check.bin
