@@ -465,7 +465,10 @@ void subtract_signal2(float *id, float *qd, long np, float f0, int shift, float 
  * spread jobs it ran (one per spot the call's decode loops added);
  * then the list-decoding stage (wspr_set_message_list(); all zero while it is off), summed like the counts: [38] the
  * stage's wall time, milliseconds (K14 and its round trips), [39] soft-symbol vectors it matched against the list, [40]
- * the spots it accepted.
+ * the spots it accepted;
+ * then the lag pruning of the drifting candidates (their own coarse pass; [29]..[31] count drift-free candidates only),
+ * summed like the counts: [41] drifting candidates pruned, [42] the exact single-lag evaluations they took, [43] drifting
+ * candidates that fell back to the whole scan.
  * Returns the number of values written (<= capacity). */
 int wspr_last_timings(double *ms, int capacity);
 /* Worker threads of the library's host pools alive in this process (the threads that call into the library are

@@ -8,7 +8,9 @@
  * WSPR_FANO_WAVE_CAP, WSPR_NODE_VIRTUAL; docs/HISTORY.md section 4 "Switches"), which read as unset in the product.
  * WSPR_K4_LAG: unset = the lag pruning (a bounded coarse pass names the lags that can still win, exact sums for those only;
  * its counts are wspr_last_timings() [29]..[31]); "full" = the whole strided scan for every drift-free candidate, as before
- * the pruning; "tile" = the same on the tiled kernel.
+ * the pruning; "tile" = the same on the tiled kernel; "nodrift" = drift-free candidates pruned, drifting ones on the whole
+ * scan (unset, the drifting candidates have a coarse pass of their own: counts [41]..[43]; "full", "tile" and
+ * WSPR_K4_DRIFT=tile keep them on the whole scan as well).
  * tests/ and bench.py load the lab library for these calls and the product library for everything else.
  * ==========================================================================*/
 #ifndef WSPR_MI355X_BENCH_H
@@ -104,7 +106,10 @@ int wspr_bench_fft_sync(const void *d_idat, const void *d_qdat, int nseg, int sa
  * and the fused frequency scan + first ladder rung (wsprd.c:721-758), and one coherent subtraction
  * (K7, wsprd.c:316-413) per segment.  ms must hold 8 doubles: ms[0] = lag scan, ms[1] = subtraction,
  * ms[2] = candidates, ms[3] = subtraction jobs, ms[4] = frequency scan + first rung (milliseconds per
- * launch set, averaged over `iters` passes after one untimed pass, as wspr_bench_fft_sync does). */
+ * launch set, averaged over `iters` passes after one untimed pass, as wspr_bench_fft_sync does).  With WSPR_BENCH_LAG_DRIFT
+ * set it first times the mode-0 lag scan of up to 2 048 DRIFTING candidates of the batch (the coarse search's own, in segment
+ * order) as launch sets alone, one untimed pass then the median of five: ms[5] = the whole scan (demod_drift_kernel +
+ * demod_metric_kernel), ms[6] = the pruned scan (coarse + fold + exact + fallbacks + list metric), ms[7] = candidates. */
 int wspr_bench_valu(const void *d_idat, const void *d_qdat, int nseg, int samples, size_t seg_stride,
                     int iters, double *ms);
 

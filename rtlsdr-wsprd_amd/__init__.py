@@ -614,7 +614,8 @@ TIMING_NAMES = (
     "osd_ms", "osd_vectors", "osd_spots", "lag_pruned", "lag_exact_evals", "lag_fallbacks",
     "block_ms", "block_vectors", "block2_decodes", "block3_decodes",
     "spread_ms", "spread_jobs",
-    "list_ms", "list_vectors", "list_spots")
+    "list_ms", "list_vectors", "list_spots",
+    "lag_drift_pruned", "lag_drift_exact_evals", "lag_drift_fallbacks")
 
 
 def last_timings():

@@ -182,7 +182,14 @@ int wspr_bench_valu(const void* d_idat, const void* d_qdat, int nseg, int sample
     try {
         Context& c = Context::get();
         c.load_device(d_idat, d_qdat, nseg, samples, seg_stride);
-        return c.bench_valu(nseg, samples, iters, ms);
+        // WSPR_BENCH_LAG_DRIFT (a measurement switch): before the stages below, the mode-0 lag scan of up to 2 048 drifting
+        // candidates of the batch as launch sets alone -> ms[5] = whole scan, ms[6] = pruned scan (ms), ms[7] = candidates
+        double dr[6] = {0};
+        const bool drift_sets = wspr::lab_env("WSPR_BENCH_LAG_DRIFT") != nullptr;
+        if (drift_sets) c.bench_lag_drift(nseg, samples, dr);
+        const int r = c.bench_valu(nseg, samples, iters, ms);
+        if (drift_sets) { ms[5] = dr[0]; ms[6] = dr[1]; ms[7] = dr[2]; }
+        return r;
     } catch (const std::exception& e) { return fail("wspr_bench_valu", e); }
 }
 

@@ -93,6 +93,7 @@ enum TimingSlot : int {
     kTmBlockMs, kTmBlockVectors, kTmBlock2Decodes, kTmBlock3Decodes,
     kTmSpreadMs, kTmSpreadJobs,
     kTmListMs, kTmListVectors, kTmListSpots,
+    kTmLagDriftPruned, kTmLagDriftExactEvals, kTmLagDriftFallbacks,
     kTimingSlots
 };
 // A batch runs on several pipelines at once and each keeps its own values; wspr_last_timings() folds them.  The stage
@@ -100,7 +101,7 @@ enum TimingSlot : int {
 // from it on is SUMMED -- the counts, and the CPU times kTmCpuMs* as well (CPU time spent on different threads adds
 // up; the public header says "summed over the slots").
 constexpr int kTimingFirstSummed = kTmFanoCalls;
-static_assert(kTimingSlots == 41 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
+static_assert(kTimingSlots == 44 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
 
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt
@@ -184,6 +185,7 @@ public:
     int last_timings(double* ms, int cap);
     int bench_fft_sync(int nseg, int samples, int iters, double* ms);
     int bench_valu(int nseg, int samples, int iters, double* ms);
+    int bench_lag_drift(int nseg, int samples, double* ms);
 
     void demod_single(float* id, float* qd, long np, unsigned char* symbols, float* freq, int ifmin, int ifmax,
                       float fstep, int* shift, int lagmin, int lagmax, int lagstep, float* drift, float* sync,

@@ -596,9 +596,9 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
     // One block up, one block down per wave (a small copy costs a blit kernel on the stream and ~10 us of
     // host time each): up = [items | launch lists], down = [items | rung-0 sync | rung-0 rms | rung-0 symbols].
     const size_t up_bytes = (size_t)nw * sizeof(FineState) + (size_t)nw * 2 * 4;
-    // (the lag pruning's three counts ride down between the rms values and the symbols)
+    // (the lag pruning's counts -- eight ints: LagPrune -- ride down between the rms values and the symbols)
     const size_t o_sync = (size_t)nw * sizeof(FineState), o_rms = o_sync + (size_t)nw * 4, o_cnt = o_rms + (size_t)nw * 4;
-    const size_t o_sym = o_cnt + 4 * 4;
+    const size_t o_sym = o_cnt + 8 * 4;
     const size_t down_bytes = o_sym + (size_t)nw * kNSymD;
     char* h_up = static_cast<char*>(c.h_items.need(up_bytes));
     char* h_down = static_cast<char*>(c.h_sym.need(std::max(down_bytes, (size_t)nw * kMaxLags * (kNSymD + 8))));
@@ -629,11 +629,12 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
     const float* wi = c.iqI.as<float>();
     const float* wq = c.iqQ.as<float>();
     LagPrune prune{c.lagprune.need(lag_prune_scratch_bytes(nw)), reinterpret_cast<int*>(d_blk + o_cnt), nullptr};
+    prune.drift = true;
     {
         Timer t(c.ev[0], c.ev[1], c.stream, &c.t_ms[kTmDemodMs]);
         upload(d_items, h_items, (size_t)nw * sizeof(FineState), c.stream);
         upload(d_lists, h_lists, (size_t)nw * 2 * 4, c.stream);
-        HIP_OK(hipMemsetAsync(prune.counts, 0, 4 * 4, c.stream));
+        HIP_OK(hipMemsetAsync(prune.counts, 0, 8 * 4, c.stream));
         // mode 0: lag scan (pruned or tiled), mode 1: 5 frequencies, mode 2: first rung of the ladder
         launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream, call_arith());
         launch_demod_tiled(wi, wq, samples, d_items, nw, d_lists, n_shared, d_lists + nw, n_own, 0, nlag0, lagstep,
@@ -669,6 +670,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
     {
         const int* cnt = reinterpret_cast<const int*>(h_down + o_cnt);
         c.t_ms[kTmLagExactEvals] += cnt[0]; c.t_ms[kTmLagFallbacks] += cnt[1]; c.t_ms[kTmLagPruned] += cnt[2];
+        c.t_ms[kTmLagDriftExactEvals] += cnt[4]; c.t_ms[kTmLagDriftFallbacks] += cnt[5]; c.t_ms[kTmLagDriftPruned] += cnt[6];
     }
     this->d_sym0 = d_sym0;                 // the list and the rescue stage read the rung-0 vectors where they lie
 
@@ -1314,6 +1316,77 @@ int Context::bench_valu(int nseg, int samples, int iters, double* ms) {
     for (auto& x : e) (void)hipEventDestroy(x);
     ms[2] = nw; ms[3] = nw;
     return 5;
+}
+
+// The mode-0 lag scan of up to 2 048 DRIFTING candidates of the resident batch (every candidate of the coarse search that has a
+// drift, in segment order), as launch sets on an otherwise idle device: the whole scan (demod_drift_kernel + demod_metric_kernel)
+// and the pruned scan (LagPrune::drift: coarse + fold + exact + fallbacks + list metric).  One untimed pass, then the median of
+// five, HIP events.  ms[0] = whole scan, ms[1] = pruned scan (milliseconds), ms[2] = candidates, ms[3] = exact evaluations,
+// ms[4] = fallbacks, ms[5] = pruned.
+int Context::bench_lag_drift(int nseg, int samples, double* ms) {
+    Impl& c = *d;
+    for (int k = 0; k < 6; ++k) ms[k] = 0.0;
+    run_fft_sync(nseg, samples, 4, true, nullptr, nseg, nullptr, nullptr);
+    std::vector<int> npk;
+    std::vector<DevCand> cand;
+    fetch_candidates(nseg, npk, cand);
+    std::vector<FineState> items;
+    for (int s = 0; s < nseg && items.size() < 2048; ++s)
+        for (int i = 0; i < npk[s] && items.size() < 2048; ++i) {
+            const DevCand& cd = cand[(size_t)s * kMaxCand + i];
+            if (cd.drift == 0.0f) continue;
+            FineState f{};
+            f.seg = s; f.freq = cd.freq; f.drift = cd.drift; f.shift = cd.shift; f.sync = cd.sync;
+            f.shift_coarse = cd.shift; f.freq_coarse = cd.freq;
+            items.push_back(f);
+        }
+    const int nw = (int)items.size();
+    if (nw == 0) return 0;
+    std::vector<int> lists(2 * (size_t)nw);
+    int n_shared = 0, n_own = 0;
+    const size_t ntabs = plan_tables(items.data(), nw, lists.data(), &n_shared, &n_own);
+    FineState* d_items = static_cast<FineState*>(c.items.need((size_t)nw * sizeof(FineState) + 8 * 4));
+    int* d_counts = reinterpret_cast<int*>(d_items + nw);
+    int* d_lists = static_cast<int*>(c.lists.need((size_t)nw * 2 * 4));
+    float* d_tabs = static_cast<float*>(c.tabs.need(std::max(ntabs, (size_t)nw * 5) * 2048 * 4));
+    float* d_pw = static_cast<float*>(c.pw.need((size_t)nw * kMaxLags * kNSymD * 16));
+    float* d_sync = static_cast<float*>(c.syncbuf.need((size_t)nw * kMaxLags * 4));
+    void* d_scratch = c.lagprune.need(lag_prune_scratch_bytes(nw));
+    HIP_OK(hipMemcpyAsync(d_items, items.data(), (size_t)nw * sizeof(FineState), hipMemcpyHostToDevice, c.stream));
+    HIP_OK(hipMemcpyAsync(d_lists, lists.data(), (size_t)nw * 2 * 4, hipMemcpyHostToDevice, c.stream));
+    launch_phasor_tables(d_items, nw, 0, d_tabs, c.stream, call_arith());
+    HIP_OK(hipStreamSynchronize(c.stream));
+    hipEvent_t e0, e1;
+    HIP_OK(hipEventCreate(&e0));
+    HIP_OK(hipEventCreate(&e1));
+    const float* wi = c.iqI.as<float>();
+    const float* wq = c.iqQ.as<float>();
+    for (int side = 0; side < 2; ++side) {
+        std::vector<float> t;
+        for (int it = -1; it < 5; ++it) {                    // pass -1 is not timed
+            LagPrune prune{d_scratch, d_counts, nullptr};
+            prune.drift = true;
+            HIP_OK(hipMemsetAsync(d_counts, 0, 8 * 4, c.stream));
+            HIP_OK(hipStreamSynchronize(c.stream));
+            HIP_OK(hipEventRecord(e0, c.stream));
+            launch_demod_tiled(wi, wq, samples, d_items, nw, d_lists, n_shared, d_lists + nw, n_own, 0, 33, 8, 0.0f, d_tabs,
+                               d_pw, d_sync, nullptr, nullptr, c.tab, c.stream, call_arith(), side ? &prune : nullptr);
+            HIP_OK(hipEventRecord(e1, c.stream));
+            HIP_OK(hipEventSynchronize(e1));
+            float v = 0;
+            HIP_OK(hipEventElapsedTime(&v, e0, e1));
+            if (it >= 0) t.push_back(v);
+        }
+        std::sort(t.begin(), t.end());
+        ms[side] = t[2];
+    }
+    int cnt[8];
+    HIP_OK(hipMemcpy(cnt, d_counts, sizeof cnt, hipMemcpyDeviceToHost));
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    ms[2] = nw; ms[3] = cnt[4]; ms[4] = cnt[5]; ms[5] = cnt[6];
+    fprintf(stderr, "bench_lag_drift: %d drifting candidates: whole scan %.3f ms, pruned scan %.3f ms; pruned %d, exact evaluations %d, "
+                    "fallbacks %d\n", nw, ms[0], ms[1], cnt[6], cnt[4], cnt[5]);
+    return 6;
 }
 
 // average duration of the whole front end (K0 a/b/c + normalise) over `iters` launches

@@ -470,6 +470,125 @@ void demod_drift_kernel(const float* __restrict__ dI, const float* __restrict__ 
     }
 }
 
+// demod_drift_kernel over the lag pruning's fallback list of drifting candidates: the list's length is in device memory, the grid
+// is sized for the longest list and surplus workgroups leave at once.  The body is a COPY of demod_drift_kernel's, statement for
+// statement, on purpose: that kernel takes 4 % of a step and is kept instruction for instruction (tools/kernel_isa_diff.py), and
+// moving its body into a function both kernels call changed its code (s_nop 75 -> 52: the shared arrays' order in LDS).  A change
+// to one of the two is a change to both (tests/test_gpu_lag_coarse_drift.py compares their rows byte for byte).
+template <bool kFma>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 3)))
+void demod_drift_list_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
+                        const FineState* __restrict__ items, const int* __restrict__ item_list,
+                        float4* __restrict__ pw_out, const int* __restrict__ nitems_dev) {
+    __shared__ float2 tile[8 * kDrPitch];
+    __shared__ float4 tab[kDrSyms * kDrTabStride];
+    constexpr int nlag = 3 * kDrGroups;
+    if ((int)blockIdx.y >= *nitems_dev) return;
+    const int item = item_list[blockIdx.y];
+    const FineState st = items[item];
+    const int i0 = blockIdx.x * kDrSyms, lane = threadIdx.x;
+    const float* __restrict__ xi = dI + (size_t)st.seg * kIqStride;
+    const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
+    const int kbase = st.shift_coarse - 128 + kSps * i0;
+#pragma unroll
+    for (int e0 = 0; e0 < kDrSpan; e0 += 64 * 8) {
+        float2 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            const int e = e0 + 64 * u + lane, k = kbase + e;
+            const bool ok = (k > 0) && (k < np);             // wsprd.c:199; zero-fill == skip (x*c = 0 adds exactly)
+            v[u] = ok ? make_float2(xi[k], xq[k]) : make_float2(0.0f, 0.0f);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) tile[drift_tile_word(e0 + 64 * u + lane)] = v[u];
+    }
+    // table lanes: (symbol, tone) recurrences, seeds as in phasor_table_kernel
+    const int bil = lane >> 2, tone = lane & 3;
+    const bool builder = lane < kDrSyms * 4;
+    float cd = 1.0f, sd = 0.0f, pc = 1.0f, ps = 0.0f;
+    if (builder) {
+        const float dphi = tone_dphi(st.freq_coarse, st.drift, i0 + bil, tone);
+        cd = glibc_cosf(dphi);
+        sd = glibc_sinf(dphi);
+    }
+    float* __restrict__ tabw = reinterpret_cast<float*>(tab + bil * kDrTabStride) + tone;
+
+    const int il = lane / kDrGroups, g = lane - il * kDrGroups;
+    const bool working = (lane < kDrSyms * kDrGroups) && (i0 + il < kNSymD);
+    const float4* __restrict__ tb = tab + (working ? il : 0) * kDrTabStride;
+    const int e_lane = 8 * g + kSps * (working ? il : 0);
+    ToneAcc<kFma> acc[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) acc[r].clear();
+    for (int ch = 0; ch < kSps / kDrChunk; ++ch) {
+        __syncthreads();                                     // the previous 32 table steps have been consumed
+        if (builder) {
+            for (int jj = 0; jj < kDrChunk; ++jj) {
+                // formed for every entry and taken from the second on (as a conditional call the exact build gains
+                // 20 register moves)
+                float nc = pc, ns = ps;
+                phasor_step<kFma>(nc, ns, cd, sd);
+                if (ch + jj > 0) { pc = nc; ps = ns; }
+                tabw[8 * jj] = pc;
+                tabw[8 * jj + 4] = ps;
+            }
+        }
+        __syncthreads();
+        if (working) {
+#pragma unroll 1
+            for (int jb = 0; jb < kDrChunk; jb += 8) {
+                const float2* __restrict__ t0[3];
+#pragma unroll
+                for (int r = 0; r < 3; ++r) {
+                    const int e = e_lane + 8 * kDrGroups * r + kDrChunk * ch + jb;      // a multiple of 8
+                    t0[r] = tile + (e >> 3) + kDrSkew * (e >> 8);
+                }
+                // operands of step u+1 are in flight while step u is consumed
+                float4 c4 = tb[2 * jb], s4 = tb[2 * jb + 1];
+                float2 d[3];
+#pragma unroll
+                for (int r = 0; r < 3; ++r) d[r] = t0[r][0];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    float4 cn = c4, sn = s4;
+                    float2 dn[3] = {d[0], d[1], d[2]};
+                    if (u + 1 < 8) {
+                        cn = tb[2 * (jb + u + 1)];
+                        sn = tb[2 * (jb + u + 1) + 1];
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) dn[r] = t0[r][(u + 1) * kDrPitch];
+                    }
+                    const v2f c01 = {c4.x, c4.y}, c23 = {c4.z, c4.w}, s01 = {s4.x, s4.y}, s23 = {s4.z, s4.w};
+                    if constexpr (kFma) {
+#pragma unroll
+                        for (int r = 0; r < 3; ++r)
+                            acc[r].step((v2f){d[r].x, d[r].x}, (v2f){d[r].y, d[r].y}, c01, c23, s01, s23);
+                    } else {
+                        // hand-scheduled (ToneAcc::products): the 24 products of a step, then the 24 accumulator updates
+                        typename ToneAcc<kFma>::Products p[3];
+#pragma unroll
+                        for (int r = 0; r < 3; ++r)
+                            p[r] = ToneAcc<kFma>::products((v2f){d[r].x, d[r].x}, (v2f){d[r].y, d[r].y}, c01, c23, s01, s23);
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) acc[r].add_x(p[r]);
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) acc[r].add_y(p[r]);
+                    }
+                    c4 = cn; s4 = sn;
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) d[r] = dn[r];
+                }
+            }
+        }
+    }
+    if (working) {
+#pragma unroll
+        for (int r = 0; r < 3; ++r)
+            pw_out[((size_t)item * nlag + g + kDrGroups * r) * kNSymD + i0 + il] = acc[r].amplitudes();
+    }
+}
+
+
 // -----------------------------------------------------------------------------
 // Lag scan (mode 0: 33 lags, step 8) of a DRIFT-FREE candidate as ONE strided correlation, samples in registers.
 //
@@ -1358,6 +1477,383 @@ void lag_exact_kernel(const float* __restrict__ dI, const float* __restrict__ dQ
     if (working) pw_out[((size_t)item * kLpLags + m) * kNSymD + tid] = acc.amplitudes();
 }
 
+// -----------------------------------------------------------------------------
+// Lag pruning (mode 0: 33 lags, step 8) of a DRIFTING candidate (LagPrune::drift; DESIGN.md section 4, "The bound for
+// drifting candidates").
+//
+// The identity holds per symbol with that symbol's frequency: with theta = the float tone_dphi(freq_coarse, drift, s, t),
+//     p_t(s, m) = | sum_{b = m}^{m + 31} B[b] |,   B[b] = sum_{j < 8} x[k0 + 256 s + 8 b + j] e^{-i theta (8 b + j)},  b = 0 .. 63
+// -- a symbol's 33 lags touch the 512 samples from 256 s on, mixed once per tone with that symbol's frequency.
+//   lag_coarse_drift_kernel        a wave = 16 symbols x 4 tones of one candidate, lane = (symbol, tone): the lane forms its 64
+//                                  block sums in registers (packed (re, im) pairs), the 33 window sums from them as
+//                                  lag_coarse_kernel does (25 shared terms + 7 + 7), the magnitudes, and its table bound
+//                                  delta_{s,t}; the wave folds them in lane order into totp~(m), ss~(m) and the largest delta
+//                                  -> part[position][wave][kCdPart].  No barrier but the fold's, no atomics.
+//   lag_coarse_drift_fold_kernel   a workgroup per candidate: T~(m) from the samples, the 11 waves' partials in wave order,
+//                                  eps(m), the contender rule and the lists: lag_coarse_kernel's final stage, term for term
+//                                  (its constants; its audit floats).
+//   lag_exact_drift_kernel         lag_exact_kernel with the lane's four phasor recurrences in registers, seeded as
+//                                  demod_drift_kernel seeds its table lanes: bytewise the rows that kernel writes.
+//   demod_drift_list_kernel        demod_drift_kernel's whole scan over the fallback list (its count read from device memory).
+// The phasors: e^{i theta} from one double sincos, its powers by double complex products (<= 20 in a row: 1e-14 with the 511-fold
+// angle error of the sincos), each rounded ONCE to float: in-block e^{i theta j}, anchors e^{i theta 8 b0} and e^{i theta 64 b1},
+// multiplied in float per block (b = 8 b1 + b0) -- the roundings of lag_coarse_kernel's e3f, e2f, e1f, so term (c) keeps 64u.
+// delta_{s,t} is MEASURED (method (ii) of DESIGN.md): a drifting candidate has no stored table, so the lane runs the table's float
+// recurrence itself, under the call's arithmetic policy, next to a double one.  The a priori bound 255 (rho + 3u)(1 + 1e-4),
+// rho = |w - e^{i theta}| (tests/lag_drift_lib.py: delta_bound) is five times the measured 1.1e-5 and sent 13 % of the drifting
+// candidates of configs[2]-shaped segments over the cap of four contenders; measured, 10 % (profiles/lag_prune_drift_bound.json).
+constexpr int kCdSyms = 16;                                            // symbols per wave
+constexpr int kCdWaves = (kNSymD + kCdSyms - 1) / kCdSyms;             // 11 waves per candidate; the last one holds 2 symbols
+constexpr int kCdPart = 2 * kLpLags + 2;                               // floats per wave: totp~[33], ss~[33], delta, spare
+
+// One lane's block sums and window magnitudes -> ps[m][lane]; kChecked: the reference's bounds test per sample (a wave that
+// hangs over the record).  Eight blocks at a time, and the windows 8 g .. 8 g + 7 (blocks 8 g .. 8 g + 38) as soon as their last
+// block exists, so that at most 40 block sums are alive; the scheduling barriers keep the compiler from forming all 64 first
+// (it then spilled 3 000 dwords).
+template <bool kChecked>
+__device__ __forceinline__ void cd_lane(const float* __restrict__ xi, const float* __restrict__ xq, int np, int kb,
+                                        const float2 (&e3)[8], const float2 (&a0)[8], const float2 (&a1)[8],
+                                        float (*__restrict__ ps)[64 + 1], int lane, bool live) {
+    v2f B[64];
+#pragma unroll
+    for (int b1 = 0; b1 < 8; ++b1) {
+#pragma unroll
+        for (int b0 = 0; b0 < 8; ++b0) {
+            const int k = kb + 8 * (8 * b1 + b0);
+            float xI[8], xQ[8];
+            if constexpr (kChecked) {
+                // wsprd.c:199: 0 < k < np; the loads are unconditional (clamped) and masked as integers, so that no branch
+                // per sample is formed
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int kk = k + j, kc = min(max(kk, 0), np - 1), keep = (kk > 0 && kk < np) ? -1 : 0;
+                    xI[j] = __builtin_bit_cast(float, __builtin_bit_cast(int, xi[kc]) & keep);
+                    xQ[j] = __builtin_bit_cast(float, __builtin_bit_cast(int, xq[kc]) & keep);
+                }
+            } else {
+                typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+                const f4u a = *reinterpret_cast<const f4u*>(xi + k), c = *reinterpret_cast<const f4u*>(xi + k + 4);
+                const f4u d = *reinterpret_cast<const f4u*>(xq + k), e = *reinterpret_cast<const f4u*>(xq + k + 4);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) { xI[j] = a[j]; xI[4 + j] = c[j]; xQ[j] = d[j]; xQ[4 + j] = e[j]; }
+            }
+            // (re, im) += (xQ, -xI) sin + (xI, xQ) cos: x e^{-i theta j} as two packed fmas
+            v2f z = {0.0f, 0.0f};
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                z = fused((v2f){xQ[j], -xI[j]}, (v2f){e3[j].y, e3[j].y}, z);
+                z = fused((v2f){xI[j], xQ[j]}, (v2f){e3[j].x, e3[j].x}, z);
+            }
+            const float2 p = a1[b1], q = a0[b0];
+            const float ca = p.x * q.x - p.y * q.y, sa = p.x * q.y + p.y * q.x;
+            B[8 * b1 + b0] = (v2f){z.x * ca + z.y * sa, z.y * ca - z.x * sa};
+            if (b0 & 1) __builtin_amdgcn_sched_barrier(0);           // the loads of two blocks in flight
+        }
+        if (b1 >= 4) {
+            // window sums W(m) = B[m] + .. + B[m + 31], eight consecutive m: the 25 blocks they share, then each one's own
+            const int g = b1 - 4;
+            v2f mid = B[8 * g + 7];
+#pragma unroll
+            for (int i = 8; i < 32; ++i) mid = mid + B[8 * g + i];
+            v2f suf = {0.0f, 0.0f}, pre = {0.0f, 0.0f}, sfx[8], pfx[8];
+            sfx[7] = suf;
+#pragma unroll
+            for (int r = 6; r >= 0; --r) { suf = suf + B[8 * g + r]; sfx[r] = suf; }
+            pfx[0] = pre;
+#pragma unroll
+            for (int r = 1; r < 8; ++r) { pre = pre + B[8 * g + 31 + r]; pfx[r] = pre; }
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const v2f w = (sfx[r] + mid) + pfx[r];
+                const float pm = __builtin_amdgcn_sqrtf(w.x * w.x + w.y * w.y);      // v_sqrt_f32: one ulp, in (c)
+                ps[8 * g + r][lane] = live ? pm : 0.0f;
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    v2f w = B[32];
+#pragma unroll
+    for (int i = 1; i < 32; ++i) w = w + B[32 + i];
+    const float pm = __builtin_amdgcn_sqrtf(w.x * w.x + w.y * w.y);
+    ps[32][lane] = live ? pm : 0.0f;
+}
+
+template <bool kFma>
+__global__ __launch_bounds__(64)
+void lag_coarse_drift_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
+                             const FineState* __restrict__ items, const int* __restrict__ item_list,
+                             const unsigned char* __restrict__ pr3, float* __restrict__ part) {
+    __shared__ float ps[kLpLags][64 + 1];
+    __shared__ float sg_s[64], dl_s[64];
+    const int pos = blockIdx.y, wave = blockIdx.x, lane = threadIdx.x;
+    const FineState st = items[item_list[pos]];
+    const float* __restrict__ xi = dI + (size_t)st.seg * kIqStride;
+    const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
+    const int sym_l = kCdSyms * wave + (lane >> 2), tone = lane & 3;
+    const bool live = sym_l < kNSymD;                                  // the last wave's spare lanes repeat symbol 161 and add 0
+    const int sym = live ? sym_l : kNSymD - 1;
+    const int kb = st.shift_coarse - 128 + kSps * sym;
+
+    const float thf = tone_dphi(st.freq_coarse, st.drift, sym, tone);
+    double s1, c1;
+    sincos((double)thf, &s1, &c1);
+    // (b) delta_{s,t}: the table the exact sums read -- demod_drift_kernel's recurrence under this arithmetic policy, from the
+    // same seeds -- against a double recurrence (255 double complex products: < 1e-12, added by the fold kernel)
+    float delta;
+    {
+        const float cd = glibc_cosf(thf), sd = glibc_sinf(thf);
+        float c = 1.0f, s = 0.0f;
+        double2 r = make_double2(1.0, 0.0);
+        const double2 z1 = make_double2(c1, s1);
+        double d2max = 0.0;
+#pragma unroll 4
+        for (int j = 1; j < kSps; ++j) {
+            phasor_step<kFma>(c, s, cd, sd);
+            r = cmul(r, z1);
+            const double dc = (double)c - r.x, ds = (double)s - r.y, d2 = dc * dc + ds * ds;
+            d2max = (d2 > d2max || d2 != d2) ? d2 : d2max;             // a NaN stays, and flags the candidate
+        }
+        delta = (float)(sqrt(d2max) * (1 + 1e-6));
+    }
+    float2 e3[8], a0[8], a1[8];
+    {
+        const double2 z1 = make_double2(c1, s1);
+        double2 z = make_double2(1.0, 0.0), z4 = z;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            e3[j] = make_float2((float)z.x, (float)z.y);
+            if (j == 4) z4 = z;
+            z = cmul(z, z1);
+        }
+        const double2 z8 = cmul(z4, z4);
+        z = make_double2(1.0, 0.0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { a0[j] = make_float2((float)z.x, (float)z.y); z = cmul(z, z8); }
+        const double2 z64 = z;
+        z = make_double2(1.0, 0.0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { a1[j] = make_float2((float)z.x, (float)z.y); z = cmul(z, z64); }
+    }
+
+    // the wave's lanes read kb .. kb + 511 each
+    const bool inside = kb > 0 && kb + 2 * kSps <= np;
+    if (__all(inside)) cd_lane<false>(xi, xq, np, kb, e3, a0, a1, ps, lane, live);
+    else cd_lane<true>(xi, xq, np, kb, e3, a0, a1, ps, lane, live);
+    // (p1 + p3) - (p0 + p2), signed by the symbol's sync bit (wsprd.c:216-217)
+    sg_s[lane] = ((tone & 1) ? 1.0f : -1.0f) * (pr3[sym] ? 1.0f : -1.0f);
+    dl_s[lane] = delta;
+    __syncthreads();
+    float* __restrict__ out = part + ((size_t)pos * kCdWaves + wave) * kCdPart;
+    if (lane < kLpLags) {
+        float totp = 0.0f, ss = 0.0f;
+        for (int l = 0; l < 64; ++l) {
+            const float p = ps[lane][l];
+            totp += p;
+            ss += sg_s[l] * p;
+        }
+        out[lane] = totp;
+        out[kLpLags + lane] = ss;
+    } else if (lane == kLpLags) {
+        float dmax = 0.0f;
+        for (int l = 0; l < 64; ++l) {
+            const float d = dl_s[l];
+            dmax = (d > dmax || d != d) ? d : dmax;
+        }
+        out[2 * kLpLags] = dmax;
+    }
+}
+
+constexpr int kCfThreads = 256;
+constexpr int kCfBlocks = 32 * kNSymD + 32;                            // 8-sample blocks under a candidate's 33 lags
+
+__global__ __launch_bounds__(kCfThreads)
+void lag_coarse_drift_fold_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
+                                  const FineState* __restrict__ items, const int* __restrict__ item_list,
+                                  const float* __restrict__ part, float* __restrict__ sync_out, int* __restrict__ counts,
+                                  int* __restrict__ exact_list, int* __restrict__ fb_list,
+                                  unsigned long long* __restrict__ mask_out, float* __restrict__ audit) {
+    __shared__ float tedge[64], tsum[kCfThreads], tsum2[16];
+    __shared__ float sy_s[kLpLags], ep_s[kLpLags];
+    __shared__ int bad_s[kLpLags];
+    __shared__ unsigned long long mask_s;
+    __shared__ int base_s;
+    const int pos = blockIdx.x, tid = threadIdx.x;
+    const int item = item_list[pos];
+    const FineState st = items[item];
+    const float* __restrict__ xi = dI + (size_t)st.seg * kIqStride;
+    const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
+    const int k0 = st.shift_coarse - 128;
+    // T: every block once; the first and last 32 blocks belong to some lags only
+    float tall = 0.0f;
+    for (int v = tid; v < kCfBlocks; v += kCfThreads) {
+        const int k = k0 + 8 * v;
+        float tb = 0.0f;
+        if (k > 0 && k + 8 <= np) {
+            typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
+            const f4u a = *reinterpret_cast<const f4u*>(xi + k), b = *reinterpret_cast<const f4u*>(xi + k + 4);
+            const f4u c = *reinterpret_cast<const f4u*>(xq + k), d = *reinterpret_cast<const f4u*>(xq + k + 4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) tb += fabsf(a[j]) + fabsf(c[j]);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) tb += fabsf(b[j]) + fabsf(d[j]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) tb += fabsf(sys_load_checked(xi, k + j, np)) + fabsf(sys_load_checked(xq, k + j, np));
+        }
+        if (v < 32) tedge[v] = tb;
+        else if (v >= 32 * kNSymD) tedge[32 + v - 32 * kNSymD] = tb;
+        else tall += tb;
+    }
+    tsum[tid] = tall;
+    __syncthreads();
+    if (tid < 16) {                                                    // a term passes 16 + 21 + 16 + 16 + 32 adds: < 256
+        float s = 0.0f;
+        for (int i = 0; i < 16; ++i) s += tsum[16 * tid + i];
+        tsum2[tid] = s;
+    }
+    __syncthreads();
+    if (tid < kLpLags) {
+        const int m = tid;
+        const float* __restrict__ pp = part + (size_t)pos * kCdWaves * kCdPart;
+        float totp = 0.0f, ss = 0.0f, tm = 0.0f, dtab = 0.0f;
+        for (int w = 0; w < kCdWaves; ++w) {
+            totp += pp[w * kCdPart + m];
+            ss += pp[w * kCdPart + kLpLags + m];
+            const float d = pp[w * kCdPart + 2 * kLpLags];
+            dtab = (d > dtab || d != d) ? d : dtab;
+        }
+        for (int i = 0; i < 16; ++i) tm += tsum2[i];
+        for (int v = m; v < 32; ++v) tm += tedge[v];                   // blocks m .. m + 5183 carry lag m's windows
+        for (int v = 0; v < m; ++v) tm += tedge[32 + v];
+        // eps(m) as lag_coarse_kernel forms it, with the largest delta_{s,t} of the candidate for delta_tab
+        const double T = (double)tm * kLpTInflate, S = (double)totp, dt = (double)dtab + 1e-12;
+        const double kappa = dt + (kLpGammaRef + 3 * kLpU * (1 + kLpGammaRef)) * (1 + dt) + kLpCoarse;
+        const double E = 4 * kappa * T + kLpGammaFold * (S + 4 * kappa * T) + kLpAbs;
+        const double r = fabs((double)ss) / S;
+        const double eps = (E * (1 + r) / (S - E) + 4 * kLpU * (1 + r)) * (1 + 1e-6);
+        const float sy = ss / totp;
+        const bool ok = (S >= kLpTotpFloor) && (S > 4 * E) && (T < kLpTCeil) && (eps == eps) && (eps < 1.0) && (sy == sy) &&
+                        (fabsf(sy) <= 2.0f);
+        sy_s[m] = sy;
+        const float ep = (float)(eps * (1 + 1e-6)) + 1e-9f;
+        ep_s[m] = ep;
+        bad_s[m] = ok ? 0 : 1;
+        if (audit) {
+            float* __restrict__ a = audit + ((size_t)item * kLpLags + m) * kLpAuditStride;
+            a[0] = sy; a[1] = ep; a[2] = totp; a[3] = ss; a[4] = tm; a[5] = dtab; a[6] = ok ? 0.0f : 1.0f;
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        bool bad = false;
+        float lo = -3.0e38f;
+        for (int m = 0; m < kLpLags; ++m) {
+            bad |= bad_s[m] != 0;
+            const float l = sy_s[m] - ep_s[m] - 1e-6f;
+            lo = l > lo ? l : lo;
+        }
+        unsigned long long mask = 0;
+        int n = 0;
+        for (int m = 0; m < kLpLags; ++m)
+            if (sy_s[m] + ep_s[m] + 1e-6f >= lo) { mask |= 1ull << m; ++n; }
+        if (bad || n > kLpCap || n == 0) {
+            fb_list[atomicAdd(&counts[1], 1)] = item;
+            mask = (1ull << kLpLags) - 1;
+            base_s = -1;
+        } else {
+            base_s = atomicAdd(&counts[0], n);
+            atomicAdd(&counts[2], 1);
+        }
+        mask_out[item] = mask;
+        mask_s = mask;
+    }
+    __syncthreads();
+    if (base_s >= 0 && tid < kLpLags) {
+        const unsigned long long mask = mask_s, bit = 1ull << tid;
+        if (mask & bit) exact_list[base_s + __builtin_popcountll(mask & (bit - 1))] = item * 64 + tid;
+        else sync_out[(size_t)item * kLpLags + tid] = -3.0e38f;        // never read (pick_lag_kernel's mask), and cannot win
+    }
+}
+
+// The reference's sums of ONE (candidate, lag) of a drifting candidate: lag_exact_kernel's staging, lane = symbol
+template <bool kFma>
+__device__ __forceinline__ void lag_exact_drift_entry(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
+                                                      const FineState* __restrict__ items, const int code,
+                                                      float2 (*__restrict__ tile)[kLxChunk + 1], float4* __restrict__ pw_out) {
+    const int item = code >> 6, m = code & 63, tid = threadIdx.x;
+    const FineState st = items[item];
+    const float* __restrict__ xi = dI + (size_t)st.seg * kIqStride;
+    const float* __restrict__ xq = dQ + (size_t)st.seg * kIqStride;
+    const int lag = st.shift_coarse - 128 + 8 * m;
+    const bool working = tid < kNSymD;
+    float2 nxt[kLxPerThread];
+    auto fetch = [&](int c) {
+#pragma unroll
+        for (int u = 0; u < kLxPerThread; ++u) {
+            const int e = u * kLxThreads + tid, row = e / kLxChunk, col = e & (kLxChunk - 1);
+            const int k = lag + kSps * row + kLxChunk * c + col;
+            const bool ok = (e < kNSymD * kLxChunk) && (k > 0) && (k < np);     // wsprd.c:199; zero-fill == skip
+            nxt[u] = ok ? make_float2(xi[k], xq[k]) : make_float2(0.0f, 0.0f);
+        }
+    };
+    fetch(0);
+    // the symbol's four recurrences (wsprd.c:158-188), seeded as demod_drift_kernel's table lanes are
+    v2f cd01 = {1.0f, 1.0f}, cd23 = cd01, sd01 = {0.0f, 0.0f}, sd23 = sd01;
+    if (working) {
+        float dphi = tone_dphi(st.freq_coarse, st.drift, tid, 0);
+        cd01.x = glibc_cosf(dphi); sd01.x = glibc_sinf(dphi);
+        dphi = tone_dphi(st.freq_coarse, st.drift, tid, 1);
+        cd01.y = glibc_cosf(dphi); sd01.y = glibc_sinf(dphi);
+        dphi = tone_dphi(st.freq_coarse, st.drift, tid, 2);
+        cd23.x = glibc_cosf(dphi); sd23.x = glibc_sinf(dphi);
+        dphi = tone_dphi(st.freq_coarse, st.drift, tid, 3);
+        cd23.y = glibc_cosf(dphi); sd23.y = glibc_sinf(dphi);
+    }
+    v2f c01 = {1.0f, 1.0f}, c23 = c01, s01 = {0.0f, 0.0f}, s23 = s01;
+    ToneAcc<kFma> acc;
+    acc.clear();
+    for (int c = 0; c < kSps / kLxChunk; ++c) {
+        __syncthreads();                                             // the previous chunk has been consumed
+#pragma unroll
+        for (int u = 0; u < kLxPerThread; ++u) {
+            const int e = u * kLxThreads + tid;
+            if (e < kNSymD * kLxChunk) tile[e / kLxChunk][e & (kLxChunk - 1)] = nxt[u];
+        }
+        __syncthreads();
+        if (c + 1 < kSps / kLxChunk) fetch(c + 1);
+        if (working) {
+#pragma unroll 8
+            for (int jj = 0; jj < kLxChunk; ++jj) {
+                if (c + jj > 0) {
+                    if constexpr (kFma) {
+                        phasor_step<kFma>(c01, s01, cd01, sd01);
+                        phasor_step<kFma>(c23, s23, cd23, sd23);
+                    } else {
+                        // the exact phasor_step() of both pairs with the eight products formed first (freq_drift_kernel)
+                        const v2f a01 = c01 * cd01, b01 = s01 * sd01, e01 = c01 * sd01, d01 = s01 * cd01;
+                        const v2f a23 = c23 * cd23, b23 = s23 * sd23, e23 = c23 * sd23, d23 = s23 * cd23;
+                        c01 = a01 - b01; s01 = e01 + d01;
+                        c23 = a23 - b23; s23 = e23 + d23;
+                    }
+                }
+                acc.step(tile[tid][jj], make_float4(c01.x, c01.y, c23.x, c23.y), make_float4(s01.x, s01.y, s23.x, s23.y));
+            }
+        }
+    }
+    if (working) pw_out[((size_t)item * kLpLags + m) * kNSymD + tid] = acc.amplitudes();
+}
+
+// One workgroup per entry of the exact list; the grid is sized for the longest list and surplus workgroups leave at once
+template <bool kFma>
+__global__ __launch_bounds__(kLxThreads)
+void lag_exact_drift_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np,
+                            const FineState* __restrict__ items, const int* __restrict__ counts,
+                            const int* __restrict__ exact_list, float4* __restrict__ pw_out) {
+    __shared__ float2 tile[kNSymD][kLxChunk + 1];
+    if ((int)blockIdx.x >= counts[0]) return;
+    lag_exact_drift_entry<kFma>(dI, dQ, np, items, exact_list[blockIdx.x], tile, pw_out);
+}
+
 // demod_metric_kernel (mode 0) over the rows the pruned scan filled: the exact list, then 33 lags per fallback candidate
 __global__ __launch_bounds__(64)
 void lag_metric_list_kernel(const float4* __restrict__ pw, const int* __restrict__ counts, const int* __restrict__ exact_list,
@@ -1517,9 +2013,10 @@ struct TiledScan {
 
 // The amplitude kernels of a tiled scan at lag step STEP: drift-free candidates, then drifting ones
 template <int STEP, bool kFma>
-void launch_tile(const TiledScan& a_in, bool shared_done) {
+void launch_tile(const TiledScan& a_in, bool shared_done, bool own_done) {
     TiledScan a = a_in;
     if (shared_done) a.n_shared = 0;                 // the lag pruning has served the drift-free candidates
+    if (own_done) a.n_own = 0;                       // ... and the drifting ones (LagPrune::drift)
     // WSPR_K4_LAG=tile: drift-free candidates' full lag scan on demod_tile_kernel<8, true> (one (symbol, lag) per lane,
     // samples in LDS) instead of the register-resident correlation
     static const bool lagsys_kernel = [] { const char* e = lab_env("WSPR_K4_LAG"); return !(e && e[0] == 't'); }();
@@ -1554,8 +2051,15 @@ void launch_tile(const TiledScan& a_in, bool shared_done) {
 }  // namespace
 
 // item_list_shared / item_list_own: indices into items[] of the candidates without / with drift
-size_t lag_prune_scratch_bytes(int nitems) {
+namespace {
+size_t lag_prune_shared_bytes(int nitems) {
     return ((size_t)nitems * 8 + (size_t)nitems * (kLpCap + 1) * 4 + 15) & ~(size_t)15;
+}
+}  // namespace
+// [contender masks | exact list | fallback list] of the drift-free candidates, then, for the drifting ones (LagPrune::drift),
+// [exact list: kLpCap x nitems | fallback list: nitems | the coarse waves' partial sums: nitems x kCdWaves x kCdPart floats]
+size_t lag_prune_scratch_bytes(int nitems) {
+    return lag_prune_shared_bytes(nitems) + (((size_t)nitems * (kLpCap + 1 + kCdWaves * kCdPart) * 4 + 15) & ~(size_t)15);
 }
 
 void launch_demod_tiled(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,
@@ -1567,18 +2071,26 @@ void launch_demod_tiled(const float* dI, const float* dQ, int samples, const Fin
     if (nitems <= 0) return;
     const TiledScan a{dI, dQ, samples, items, list_shared, list_own, n_shared, n_own, mode, nlag, minsync1, tabs,
                       reinterpret_cast<float4*>(pw), st};
-    // WSPR_K4_LAG=full (or tile): every drift-free candidate through the whole scan, as before the lag pruning
+    // WSPR_K4_LAG=full (or tile): every candidate through the whole scan, as before the lag pruning; =nodrift: the drift-free
+    // candidates are pruned, the drifting ones take the whole scan (as before they had a pruning of their own)
     static const bool whole_scan = [] { const char* e = lab_env("WSPR_K4_LAG"); return e && (e[0] == 'f' || e[0] == 't'); }();
-    const bool pruned = prune && !whole_scan && mode == 0 && lagstep == 8 && nlag == kLpLags && n_shared > 0;
+    static const bool nodrift = [] { const char* e = lab_env("WSPR_K4_LAG"); return e && e[0] == 'n'; }();
+    static const bool drift_tile = [] { const char* e = lab_env("WSPR_K4_DRIFT"); return e && e[0] == 't'; }();
+    const bool prunable = prune && !whole_scan && mode == 0 && lagstep == 8 && nlag == kLpLags;
+    const bool pruned = prunable && n_shared > 0;
+    const bool pruned_own = prunable && prune->drift && !nodrift && !drift_tile && n_own > 0;
     with_arith(arith, [&](auto fma) {
         constexpr bool kFma = decltype(fma)::value;
+        unsigned long long* mask = nullptr;
+        if (pruned || pruned_own) {
+            mask = reinterpret_cast<unsigned long long*>(prune->scratch);
+            prune->mask = mask;
+            (void)hipMemsetAsync(mask, 0xff, (size_t)nitems * 8, st);            // candidates that are not pruned: every lag
+        }
         if (pruned) {
             // scratch: [contender masks: nitems x 8 bytes | exact list: kLpCap x n_shared | fallback list: n_shared]
-            unsigned long long* mask = reinterpret_cast<unsigned long long*>(prune->scratch);
             int* exact_list = reinterpret_cast<int*>(mask + nitems);
-            prune->mask = mask;
             int* fb_list = exact_list + (size_t)kLpCap * n_shared;
-            (void)hipMemsetAsync(mask, 0xff, (size_t)nitems * 8, st);            // drifting candidates: every lag
             hipLaunchKernelGGL(lag_coarse_kernel, dim3(8 * ((n_shared + 7) >> 3)), dim3(kCoThreads), 0, st, dI, dQ, samples,
                                items, list_shared, n_shared, tabs, t.sync, sync_out, prune->counts, exact_list, fb_list,
                                mask, prune->audit);
@@ -1589,13 +2101,29 @@ void launch_demod_tiled(const float* dI, const float* dQ, int samples, const Fin
             hipLaunchKernelGGL(lag_metric_list_kernel, dim3(((kLpCap + kLpLags) * n_shared + 63) / 64), dim3(64), 0, st,
                                a.pw4, prune->counts, exact_list, fb_list, sync_out, t.sync);
         }
-        if (lagstep == 8) launch_tile<8, kFma>(a, pruned);
-        else if (lagstep == 16) launch_tile<16, kFma>(a, pruned);
-        else launch_tile<3, kFma>(a, pruned);
-        if (!pruned)
+        if (pruned_own) {
+            int* exact_list = reinterpret_cast<int*>(static_cast<char*>(prune->scratch) + lag_prune_shared_bytes(nitems));
+            int* fb_list = exact_list + (size_t)kLpCap * nitems;
+            float* part = reinterpret_cast<float*>(fb_list + nitems);
+            int* counts = prune->counts + 4;
+            hipLaunchKernelGGL(lag_coarse_drift_kernel<kFma>, dim3(kCdWaves, n_own), dim3(64), 0, st, dI, dQ, samples, items, list_own,
+                               t.sync, part);
+            hipLaunchKernelGGL(lag_coarse_drift_fold_kernel, dim3(n_own), dim3(kCfThreads), 0, st, dI, dQ, samples, items,
+                               list_own, part, sync_out, counts, exact_list, fb_list, mask, prune->audit);
+            hipLaunchKernelGGL(lag_exact_drift_kernel<kFma>, dim3(kLpCap * n_own), dim3(kLxThreads), 0, st, dI, dQ, samples,
+                               items, counts, exact_list, a.pw4);
+            hipLaunchKernelGGL(demod_drift_list_kernel<kFma>, dim3((kNSymD + kDrSyms - 1) / kDrSyms, n_own), dim3(64), 0, st, dI,
+                               dQ, samples, items, fb_list, a.pw4, counts + 1);
+            hipLaunchKernelGGL(lag_metric_list_kernel, dim3(((kLpCap + kLpLags) * n_own + 63) / 64), dim3(64), 0, st, a.pw4,
+                               counts, exact_list, fb_list, sync_out, t.sync);
+        }
+        if (lagstep == 8) launch_tile<8, kFma>(a, pruned, pruned_own);
+        else if (lagstep == 16) launch_tile<16, kFma>(a, pruned, pruned_own);
+        else launch_tile<3, kFma>(a, pruned, pruned_own);
+        if (!pruned && !pruned_own)
             hipLaunchKernelGGL(demod_metric_kernel<kFma>, dim3((nitems * nlag + 63) / 64), dim3(64), 0, st, a.pw4, items, nitems,
                                mode, nlag, minsync1, sync_out, sym_out, rms_out, t.sync);
-        else if (n_own > 0)
+        else if (!pruned_own && n_own > 0)
             hipLaunchKernelGGL(demod_metric_kernel<kFma>, dim3((n_own * nlag + 63) / 64), dim3(64), 0, st, a.pw4, items, n_own,
                                mode, nlag, minsync1, sync_out, sym_out, rms_out, t.sync, list_own);
     });

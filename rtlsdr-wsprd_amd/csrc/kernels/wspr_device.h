@@ -145,11 +145,16 @@ void launch_phasor_tables(const FineState* items, int nitems, int mode, float* t
 // when it did not prune) for launch_pick_lag().  `audit` (null everywhere but in tools/lagprune_check.hip): nitems x 33 x 7
 // floats of device memory that receive the coarse pass' own numbers per (item, lag) -- sync~, eps, totp~, ss~, T~, delta_tab,
 // flagged bad (1.0f / 0.0f) -- for the drift-free candidates; see the pruning block of k4_demod.hip.
+// `drift` (opt-in; the decode pipeline sets it): the drifting candidates are pruned as well, by kernels of their own
+// (lag_coarse_drift_kernel ...).  `counts` is then EIGHT zeroed ints: [4] exact single-lag evaluations, [5] fallbacks and
+// [6] candidates pruned among the drifting ones; their lists follow the drift-free ones in `scratch`, and `audit` receives
+// their rows too.  A drifting candidate that falls back takes demod_drift_kernel's whole scan.  Off: drifting candidates take the whole scan, mask all ones, counts[4..] and the rest of scratch untouched.
 struct LagPrune {
     void* scratch;
     int* counts;
     const unsigned long long* mask;
     float* audit = nullptr;
+    bool drift = false;
 };
 size_t lag_prune_scratch_bytes(int nitems);
 void launch_demod_tiled(const float* dI, const float* dQ, int samples, const FineState* items, int nitems,

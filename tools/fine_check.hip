@@ -64,7 +64,9 @@ static int fresh(void** p, size_t bytes) {
 #define FRESH(p, bytes) do { const int r_ = fresh(reinterpret_cast<void**>(&(p)), bytes); if (r_) return r_; } while (0)
 
 int main(int argc, char** argv) {
-    if (argc != 3) { fprintf(stderr, "usage: %s case.bin out.bin\n", argv[0]); return 2; }
+    // a third argument "drift": the pruned scan also prunes the drifting candidates (LagPrune::drift); the dump format is the same
+    if (argc != 3 && !(argc == 4 && !strcmp(argv[3], "drift"))) { fprintf(stderr, "usage: %s case.bin out.bin [drift]\n", argv[0]); return 2; }
+    const bool drift = argc == 4;
     FILE* in = fopen(argv[1], "rb");
     FILE* out = fopen(argv[2], "wb");
     NEED(in && out);
@@ -118,7 +120,7 @@ int main(int argc, char** argv) {
         unsigned char *sym_r0, *sym_l;
         void* scratch;
         OK(hipMalloc(&d_items, item_bytes)); OK(hipMalloc(&d_lists, 2 * n * 4));
-        FRESH(counts, 16); FRESH(tabs, tab_bytes); FRESH(tabs1, tab_bytes); FRESH(pw, pw_bytes); FRESH(pwf, pwf_bytes);
+        FRESH(counts, 32); FRESH(tabs, tab_bytes); FRESH(tabs1, tab_bytes); FRESH(pw, pw_bytes); FRESH(pwf, pwf_bytes);
         FRESH(scr, (size_t)n * kNFreq * 4); FRESH(sync0, (size_t)n * kMaxLags * 4); FRESH(sync_r0, (size_t)n * 4);
         FRESH(rms_r0, (size_t)n * 4); FRESH(sym_r0, (size_t)n * kNSymD); FRESH(sync_l, (size_t)n * kMaxLags * 4);
         FRESH(rms_l, (size_t)n * kMaxLags * 4); FRESH(sym_l, (size_t)n * kMaxLags * kNSymD); FRESH(scratch, scratch_bytes);
@@ -132,8 +134,9 @@ int main(int argc, char** argv) {
 
         // mode 0: the lag scan and its pick
         LagPrune prune{scratch, counts, nullptr};
+        prune.drift = drift;
         if (flags & kRunMode0) {
-            OK(hipMemsetAsync(counts, 0, 4 * 4, 0));
+            OK(hipMemsetAsync(counts, 0, 8 * 4, 0));
             launch_phasor_tables(d_items, n, 0, tabs, 0, arith);
             launch_demod_tiled(dI, dQ, np, d_items, n, d_lists, n_shared, d_lists + n, n_own, 0, nlag, lagstep, 0.0f, tabs, pw,
                                sync0, nullptr, nullptr, t, 0, arith, (flags & kPrune) ? &prune : nullptr);

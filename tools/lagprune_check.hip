@@ -10,6 +10,9 @@
 // Output file, per run: int32 nitems, n_shared, n_own, scratch_bytes; float tabs[nitems][2048]; FineState after A, after B;
 // float sync_A[nitems][33], sync_B; float pw_A[nitems][33][162][4], pw_B; the pruning's scratch (masks: nitems x 8 bytes,
 // exact list: 4 n_shared ints, fallback list: n_shared ints); int32 counts[4]; float audit[nitems][33][7].
+// With a third argument "drift" the pruned run also prunes the drifting candidates (LagPrune::drift) and every run's dump
+// ends with int32 counts[4..7] (drifting candidates: exact evaluations, fallbacks, pruned, unused); their lists are in the
+// scratch dump behind the drift-free ones (lag_prune_scratch_bytes() in k4_demod.hip gives the layout).
 // Every output buffer starts as bytes of 0xa5 (as a float: -2.87e-16), so what no kernel wrote can be told.
 #include "../rtlsdr-wsprd_amd/csrc/kernels/k4_demod.hip"
 #include <cstdio>
@@ -34,7 +37,8 @@ static int dump(FILE* out, const void* dev, size_t bytes, std::vector<char>& hos
 #define DUMP(dev, bytes) do { const int r_ = dump(out, dev, bytes, host); if (r_) return r_; } while (0)
 
 int main(int argc, char** argv) {
-    if (argc != 3) { fprintf(stderr, "usage: %s case.bin out.bin\n", argv[0]); return 2; }
+    if (argc != 3 && !(argc == 4 && !strcmp(argv[3], "drift"))) { fprintf(stderr, "usage: %s case.bin out.bin [drift]\n", argv[0]); return 2; }
+    const bool drift = argc == 4;
     FILE* in = fopen(argv[1], "rb");
     FILE* out = fopen(argv[2], "wb");
     NEED(in && out);
@@ -84,7 +88,7 @@ int main(int argc, char** argv) {
         float *tabs, *pwA, *pwB, *syA, *syB, *audit;
         void* scratch;
         OK(hipMalloc(&itA, n * sizeof(FineState))); OK(hipMalloc(&itB, n * sizeof(FineState)));
-        OK(hipMalloc(&dls, lists.size() * 4 + 4)); OK(hipMalloc(&counts, 16)); OK(hipMalloc(&tabs, tab_bytes));
+        OK(hipMalloc(&dls, lists.size() * 4 + 4)); OK(hipMalloc(&counts, 32)); OK(hipMalloc(&tabs, tab_bytes));
         OK(hipMalloc(&pwA, pw_bytes)); OK(hipMalloc(&pwB, pw_bytes)); OK(hipMalloc(&syA, nrow * 4)); OK(hipMalloc(&syB, nrow * 4));
         OK(hipMalloc(&audit, audit_bytes)); OK(hipMalloc(&scratch, scratch_bytes));
         dlo = dls + n_shared;
@@ -93,12 +97,13 @@ int main(int argc, char** argv) {
         OK(hipMemcpy(dls, lists.data(), lists.size() * 4, hipMemcpyHostToDevice));
         OK(hipMemset(tabs, kSentinel, tab_bytes)); OK(hipMemset(pwA, kSentinel, pw_bytes)); OK(hipMemset(pwB, kSentinel, pw_bytes));
         OK(hipMemset(syA, kSentinel, nrow * 4)); OK(hipMemset(syB, kSentinel, nrow * 4)); OK(hipMemset(audit, kSentinel, audit_bytes));
-        OK(hipMemset(scratch, kSentinel, scratch_bytes)); OK(hipMemset(counts, kSentinel, 16));
+        OK(hipMemset(scratch, kSentinel, scratch_bytes)); OK(hipMemset(counts, kSentinel, 32));
         OK(hipDeviceSynchronize());
 
         // A: the pruned scan, as wspr_pipeline.hip runs it, with the audit output
         LagPrune prune{scratch, counts, nullptr, audit};
-        OK(hipMemsetAsync(counts, 0, 4 * 4, 0));
+        prune.drift = drift;
+        OK(hipMemsetAsync(counts, 0, (drift ? 8 : 4) * 4, 0));
         launch_phasor_tables(itA, n, 0, tabs, 0, arith);
         launch_demod_tiled(dI, dQ, np, itA, n, dls, n_shared, dlo, n_own, 0, kLpLags, 8, 0.0f, tabs, pwA, syA, nullptr, nullptr, t,
                            0, arith, &prune);
@@ -122,6 +127,7 @@ int main(int argc, char** argv) {
         DUMP(syA, nrow * 4); DUMP(syB, nrow * 4);
         DUMP(pwA, pw_bytes); DUMP(pwB, pw_bytes);
         DUMP(scratch, scratch_bytes); DUMP(counts, 16); DUMP(audit, audit_bytes);
+        if (drift) DUMP(counts + 4, 16);
         OK(hipFree(itA)); OK(hipFree(itB)); OK(hipFree(dls)); OK(hipFree(counts)); OK(hipFree(tabs)); OK(hipFree(pwA));
         OK(hipFree(pwB)); OK(hipFree(syA)); OK(hipFree(syB)); OK(hipFree(audit)); OK(hipFree(scratch));
     }
