@@ -252,6 +252,39 @@ int wspr_audio_to_iq(const int16_t *pcm, size_t nsamp, float *I, float *Q, uint3
 /* The two tables of 511 taps (index k + 255) and the input samples per output (32) as the kernel uses them. */
 void wspr_audio_constants(float *taps_i511, float *taps_q511, int *samples_per_output /* 32 */);
 
+/* ---- impulse-noise blanker in front of the audio front end (K15), opt-in ----------------------------------------
+ * Lightning static, electric fences and switching supplies put short, huge spikes into the 12 kHz audio; the 511 taps of
+ * K12 smear each over 43 ms of the IQ.  The blanker acts on the wide-band samples, before that filter.  All integer
+ * (rtlsdr-wsprd_amd/csrc/kernels/audio_blank.h; tests/helpers/blank_check.c is the contract in serial C):
+ *   a[n] = |pcm[n]| (-32768 gives 32768).  Block b = samples 8192 b .. min(8192 (b + 1), nsamp) - 1 (one WSPR symbol).
+ *   L_b  = the lower median of the block's a[]: rank (count - 1) / 2 of its own samples inside the record.
+ *   out[n] = 0 if L_b > 0 and some n' in [max(0, n - guard), min(nsamp - 1, n + guard)] has 16 a[n'] > thr16 L_b (strict),
+ *   else pcm[n]; b is the block of n, and a neighbour n' in the next or the previous block is judged by L_b as well.
+ *   A block with L_b == 0 (digital silence) is copied.  thr16 = 16 .. 4096 (sixteenths of the level), guard = 0 .. 64.
+ * n_blanked[s] = the samples of record s for which the condition held.  thr16 = 4096 blanks nothing unless a sample is
+ * 256 times the level; (96, 4) is what the figures in the README were measured with.
+ * The settings are arguments, not state: wspr_audio_batch_device(), wspr_audio_to_iq() and every decode call are
+ * untouched by these calls.
+ *
+ * K15 alone: nseg PCM rows in HBM -> nseg blanked PCM rows in HBM (row s at d_out + s*out_stride samples).  d_pcm, pcm_stride
+ * as for wspr_audio_batch_device(); d_out 16-byte aligned, out_stride a multiple of 8 and >= nsamp.  Columns
+ * 0 .. roundup8(nsamp) - 1 of an output row are written (zero from nsamp on), the columns behind are left alone.
+ * Returns 0; -1 with a line on stderr and NOTHING WRITTEN (n_blanked included) for: no device, nseg < 0, nsamp < 0,
+ * misalignment, a stride that is no multiple of 8 or is too small, thr16 outside 16 .. 4096, guard outside 0 .. 64, output
+ * rows that overlap the input rows (in place is a race: a neighbouring block would read blanked samples); -2 for
+ * nsamp > 1 440 000.  nseg == 0 does nothing, nsamp == 0 writes no sample (n_blanked: zeros).  Stream contract and lane
+ * turn as wspr_audio_batch_device(). */
+int wspr_audio_blank_batch_device(const void *d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard,
+                                  void *d_out, size_t out_stride, int *n_blanked /* host, nseg, may be NULL */);
+/* K15 then K12: what wspr_audio_batch_device() does, on blanked samples; refusals as above (nsamp == 0 writes zero rows).
+ * The blanked samples pass through scratch rows of the lane's context, at most 128 records (369 MB) at a time however large
+ * nseg is; wspr_release_buffers() returns them. */
+int wspr_audio_blanked_batch_device(const void *d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard,
+                                    void *d_idat, void *d_qdat, int normalise, int *n_blanked /* host, nseg, may be NULL */);
+/* one record from host memory, as wspr_audio_to_iq(); n_blanked: one int, may be NULL */
+int wspr_audio_to_iq_blanked(const int16_t *pcm, size_t nsamp, int thr16, int guard, float *I, float *Q,
+                             uint32_t *n_out, int normalise, int *n_blanked);
+
 /* ---- signal synthesiser (K8) ------------------------------------------------------------------------------
  * The reference's self-test generator (decoderSelfTest() / whiteGaussianNoise(), rtlsdr_wsprd.c:706-760) for batches
  * of scenes resident in HBM: from "symbols, frequency, time, level" to the IQ rows wspr_decode_batch_device() takes,

@@ -171,6 +171,15 @@ def _bind(path):
     L.wspr_audio_to_iq.restype = C.c_int
     L.wspr_audio_constants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.wspr_audio_constants.restype = None
+    L.wspr_audio_blank_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                C.c_size_t, C.c_void_p]
+    L.wspr_audio_blank_batch_device.restype = C.c_int
+    L.wspr_audio_blanked_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                                  C.c_void_p, C.c_int, C.c_void_p]
+    L.wspr_audio_blanked_batch_device.restype = C.c_int
+    L.wspr_audio_to_iq_blanked.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_int, C.c_void_p]
+    L.wspr_audio_to_iq_blanked.restype = C.c_int
     L.wspr_read_wav_file.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
     L.wspr_read_wav_file.restype = C.c_size_t
     L.wspr_selftest.argtypes = [decoder_options, C.c_void_p]
@@ -491,6 +500,36 @@ def audio_to_iq(pcm, normalise=0):
     if rc != 0:
         raise RuntimeError("wspr_audio_to_iq failed (rc %d: a record above 120 s, or no usable HIP device)" % rc)
     return I, Q, int(n_out.value)
+
+
+def audio_blank_batch_device(d_pcm, pcm_stride, nsamp, nseg, thr16, guard, d_out, out_stride, n_blanked=None):
+    """wspr_audio_blank_batch_device(): the impulse-noise blanker (K15) alone, PCM rows at the raw device pointer d_pcm into
+    PCM rows at d_out.  n_blanked: an int32 numpy array of nseg that receives the blanked samples per record, or None.
+    Returns the library's code (0; -1 with nothing written; -2 for nsamp > AUDIO_MAX_SAMPLES)."""
+    return lib().wspr_audio_blank_batch_device(d_pcm, int(pcm_stride), int(nsamp), int(nseg), int(thr16), int(guard), d_out,
+                                               int(out_stride), None if n_blanked is None else _ptr(n_blanked))
+
+
+def audio_blanked_batch_device(d_pcm, pcm_stride, nsamp, nseg, thr16, guard, d_i, d_q, normalise=0, n_blanked=None):
+    """wspr_audio_blanked_batch_device(): audio_batch_device() on blanked samples (K15 then K12); n_blanked as above."""
+    return lib().wspr_audio_blanked_batch_device(d_pcm, int(pcm_stride), int(nsamp), int(nseg), int(thr16), int(guard), d_i,
+                                                 d_q, int(normalise), None if n_blanked is None else _ptr(n_blanked))
+
+
+def audio_to_iq_blanked(pcm, thr16, guard, normalise=0):
+    """wspr_audio_to_iq_blanked(): audio_to_iq() on blanked samples.  Returns (I, Q, n_out, n_blanked); raises if the
+    library refuses the call."""
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    I = np.zeros(NSAMPLES, np.float32)
+    Q = np.zeros(NSAMPLES, np.float32)
+    n_out = C.c_uint32(0)
+    n_blanked = C.c_int(0)
+    rc = lib().wspr_audio_to_iq_blanked(_ptr(pcm), int(pcm.size), int(thr16), int(guard), _ptr(I), _ptr(Q),
+                                        C.addressof(n_out), int(normalise), C.addressof(n_blanked))
+    if rc != 0:
+        raise RuntimeError("wspr_audio_to_iq_blanked failed (rc %d: settings out of range, a record above 120 s, or no usable "
+                           "HIP device)" % rc)
+    return I, Q, int(n_out.value), int(n_blanked.value)
 
 
 def read_wav_file(filename, cap=AUDIO_MAX_SAMPLES):

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "wspr_capi_impl.h"
+#include "../kernels/audio_blank.h"
 #include "../kernels/audio_front.h"
 
 using wspr::Context;
@@ -171,6 +172,76 @@ int wspr_audio_to_iq(const int16_t* pcm, size_t nsamp, float* I, float* Q, uint3
         if (n_out) *n_out = (uint32_t)audio_front_n_out((int)nsamp);
         return 0;
     } catch (const std::exception& e) { return fail("wspr_audio_to_iq", e); }
+}
+
+// ---- K15, the impulse-noise blanker in front of K12 (kernels/audio_blank.h) -------------------------------------------
+static int blank_settings_bad(const char* where, int thr16, int guard) {
+    if (audio_blank_settings_ok(thr16, guard)) return 0;
+    fprintf(stderr, "libwspr_mi355x: %s: thr16 must be 16 .. 4096 and guard 0 .. 64\n", where);
+    return -1;
+}
+
+int wspr_audio_blank_batch_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, void* d_out,
+                                  size_t out_stride, int* n_blanked) {
+    static const char* where = "wspr_audio_blank_batch_device";
+    LaneTurn lane_turn;
+    try {
+        if (const int bad = blank_settings_bad(where, thr16, guard)) return bad;
+        // (the counts' and the input's checks are K12's: its output checks see the input again and pass)
+        if (const int bad = audio_args_bad(where, d_pcm, pcm_stride, nsamp, nseg, d_pcm, d_pcm)) return bad;
+        if (nseg == 0) return 0;
+        const char* why = nullptr;
+        const size_t padded = ((size_t)nsamp + 7) & ~(size_t)7;
+        const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_pcm), out0 = reinterpret_cast<uintptr_t>(d_out);
+        const uintptr_t in1 = in0 + (((size_t)nseg - 1) * pcm_stride + padded) * sizeof(int16_t);
+        const uintptr_t out1 = out0 + (((size_t)nseg - 1) * out_stride + padded) * sizeof(int16_t);
+        if (!d_out || (out0 & 15)) why = "d_out must be 16-byte aligned device memory";
+        else if ((out_stride & 7) || out_stride < (size_t)nsamp) why = "out_stride must be a multiple of 8 and at least nsamp";
+        // in place is a race: a neighbouring block's halo would read samples that are already blanked
+        else if (nsamp > 0 && in0 < out1 && out0 < in1) why = "the output rows overlap the input rows";
+        if (why) { fprintf(stderr, "libwspr_mi355x: %s: %s\n", where, why); return -1; }
+        return Context::get().audio_blank_device(d_pcm, pcm_stride, nsamp, nseg, thr16, guard, d_out, out_stride, n_blanked);
+    } catch (const std::exception& e) { return fail(where, e); }
+}
+
+int wspr_audio_blanked_batch_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard,
+                                    void* d_idat, void* d_qdat, int normalise, int* n_blanked) {
+    static const char* where = "wspr_audio_blanked_batch_device";
+    LaneTurn lane_turn;
+    try {
+        if (const int bad = blank_settings_bad(where, thr16, guard)) return bad;
+        if (const int bad = audio_args_bad(where, d_pcm, pcm_stride, nsamp, nseg, d_idat, d_qdat)) return bad;
+        return Context::get().audio_blanked_device(d_pcm, pcm_stride, nsamp, nseg, thr16, guard, (float*)d_idat, (float*)d_qdat,
+                                                   normalise, n_blanked);
+    } catch (const std::exception& e) { return fail(where, e); }
+}
+
+int wspr_audio_to_iq_blanked(const int16_t* pcm, size_t nsamp, int thr16, int guard, float* I, float* Q, uint32_t* n_out,
+                             int normalise, int* n_blanked) {
+    static const char* where = "wspr_audio_to_iq_blanked";
+    LaneTurn lane_turn;
+    try {
+        if (const int bad = blank_settings_bad(where, thr16, guard)) return bad;
+        if (nsamp > (size_t)AUDIO_FRONT_MAX_SAMPLES) return audio_args_bad(where, nullptr, 0, (long long)AUDIO_FRONT_MAX_SAMPLES + 1, 0, nullptr, nullptr);
+        if ((!pcm && nsamp) || !I || !Q) { fprintf(stderr, "libwspr_mi355x: %s: no record, or no output rows\n", where); return -1; }
+        Context& c = Context::get();
+        int16_t* d_pcm = c.audio_pcm(nsamp);
+        if (nsamp) HIP_TRY(hipMemcpy(d_pcm, pcm, nsamp * sizeof(int16_t), hipMemcpyHostToDevice));
+        float* wi = c.work_i(1);
+        float* wq = c.work_q(1);
+        int blanked = 0;
+        const int rc = c.audio_blanked_device(d_pcm, (nsamp + 7) & ~(size_t)7, (int)nsamp, 1, thr16, guard, wi, wq, normalise, &blanked);
+        if (rc) return rc;
+        const size_t bytes = (size_t)wspr::kMaxSamples * sizeof(float);
+        std::vector<float> oi(wspr::kMaxSamples), oq(wspr::kMaxSamples);    // both rails arrive before either is handed over
+        HIP_TRY(hipMemcpy(oi.data(), wi, bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(oq.data(), wq, bytes, hipMemcpyDeviceToHost));
+        std::memcpy(I, oi.data(), bytes);
+        std::memcpy(Q, oq.data(), bytes);
+        if (n_out) *n_out = (uint32_t)audio_front_n_out((int)nsamp);
+        if (n_blanked) *n_blanked = blanked;
+        return 0;
+    } catch (const std::exception& e) { return fail(where, e); }
 }
 
 void wspr_audio_constants(float* taps_i511, float* taps_q511, int* samples_per_output) {

@@ -193,7 +193,8 @@ size_t Context::release_buffers() {
                               &c.symbuf, &c.rmsbuf, &c.jobs, &c.subscratch, &c.nvalid, &c.decscratch, &c.tabs, &c.pw, &c.pwfreq, &c.lagprune,
                               &c.lists, &c.scrsync, &c.psavg, &c.densein, &c.fz_sym, &c.fz_off, &c.fz_ret, &c.fz_cyc, &c.fz_met, &c.fz_max,
                               &c.fz_dat, &c.fz_steps, &c.fz_pool, &c.streamraw, &c.streamstate, &c.synthtx, &c.synthoff, &c.synthfirst,
-                              &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out, &c.spr_tw, &c.spr_jobs, &c.spr_ckpt, &c.spr_out, &c.audiopcm, &c.synthfade, &c.list_out})
+                              &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out, &c.spr_tw, &c.spr_jobs, &c.spr_ckpt, &c.spr_out, &c.audiopcm, &c.synthfade, &c.list_out,
+                              &c.blankrows, &c.blankcount})
                 freed += b->release();
             for (PinBuf* b : {&c.h_npk, &c.h_cand, &c.h_items, &c.h_sync, &c.h_sym, &c.h_rms, &c.h_jobs, &c.h_jobs2, &c.h_seglist,
                               &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_sprjobs, &c.h_sprout, &c.h_list, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
@@ -660,6 +661,60 @@ int Context::audio_device(const void* d_pcm, size_t pcm_stride, int nsamp, int n
     launch_audio_front(static_cast<const int16_t*>(d_pcm), pcm_stride, nsamp, nseg, dI, dQ, c.stream);
     if (normalise) launch_normalise(dI, dQ, nullptr, nseg, kMaxSamples, c.stream);
     HIP_OK(hipGetLastError());
+    if (c.blocking) {
+        HIP_OK(hipEventRecord(c.ev_sync, c.stream));
+        host_wait(c.ev_sync);
+    } else {
+        HIP_OK(hipStreamSynchronize(c.stream));
+    }
+    return 0;
+}
+
+// K15: the blanker on the lane's stream; the records' counters come back with it
+int Context::audio_blank_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, void* d_out,
+                                size_t out_stride, int* h_blanked) {
+    Impl& c = *d;
+    if (nseg <= 0) return 0;
+    int* d_count = static_cast<int*>(c.blankcount.need((size_t)nseg * sizeof(int)));
+    HIP_OK(hipMemsetAsync(d_count, 0, (size_t)nseg * sizeof(int), c.stream));
+    launch_audio_blank(static_cast<const int16_t*>(d_pcm), pcm_stride, nsamp, nseg, thr16, guard, static_cast<int16_t*>(d_out),
+                       out_stride, d_count, c.stream);
+    HIP_OK(hipGetLastError());
+    if (h_blanked) HIP_OK(hipMemcpyAsync(h_blanked, d_count, (size_t)nseg * sizeof(int), hipMemcpyDeviceToHost, c.stream));
+    if (c.blocking) {
+        HIP_OK(hipEventRecord(c.ev_sync, c.stream));
+        host_wait(c.ev_sync);
+    } else {
+        HIP_OK(hipStreamSynchronize(c.stream));
+    }
+    return 0;
+}
+
+// K15 then K12, kBlankChunk records at a time through the context's scratch rows (both kernels on the lane's stream, so a
+// chunk's K15 waits for the K12 that still reads the rows): the scratch never exceeds kBlankChunk rows, whatever nseg is
+int Context::audio_blanked_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, float* dI,
+                                  float* dQ, int normalise, int* h_blanked) {
+    Impl& c = *d;
+    if (nseg <= 0) return 0;
+    const size_t row = ((size_t)nsamp + 7) & ~(size_t)7;
+    const size_t bytes = (size_t)std::min(nseg, kBlankChunk) * row * sizeof(int16_t) + 16;
+    if (bytes > c.blankrows.cap) {                            // exactly what is needed: need() would add a quarter to 369 MB
+        c.blankrows.release();
+        HIP_OK(hipMalloc(&c.blankrows.p, bytes));
+        c.blankrows.cap = bytes;
+    }
+    int16_t* rows = c.blankrows.as<int16_t>();
+    int* d_count = static_cast<int*>(c.blankcount.need((size_t)nseg * sizeof(int)));
+    HIP_OK(hipMemsetAsync(d_count, 0, (size_t)nseg * sizeof(int), c.stream));
+    const int16_t* in = static_cast<const int16_t*>(d_pcm);
+    for (int s0 = 0; s0 < nseg; s0 += kBlankChunk) {
+        const int n = std::min(kBlankChunk, nseg - s0);
+        launch_audio_blank(in + (size_t)s0 * pcm_stride, pcm_stride, nsamp, n, thr16, guard, rows, row, d_count + s0, c.stream);
+        launch_audio_front(rows, row, nsamp, n, dI + (size_t)s0 * kIqStride, dQ + (size_t)s0 * kIqStride, c.stream);
+    }
+    if (normalise) launch_normalise(dI, dQ, nullptr, nseg, kMaxSamples, c.stream);
+    HIP_OK(hipGetLastError());
+    if (h_blanked) HIP_OK(hipMemcpyAsync(h_blanked, d_count, (size_t)nseg * sizeof(int), hipMemcpyDeviceToHost, c.stream));
     if (c.blocking) {
         HIP_OK(hipEventRecord(c.ev_sync, c.stream));
         host_wait(c.ev_sync);

@@ -247,7 +247,8 @@ struct Context::Impl {
     DevBuf iqI, iqQ, ps, cand, npk, noise, smspec, seglist, items, syncbuf, symbuf, rmsbuf, jobs, subscratch,
         nvalid, decscratch, tabs, pw, pwfreq, lagprune, lists, scrsync, psavg, densein, fz_sym, fz_off, fz_ret, fz_cyc, fz_met, fz_max, fz_dat, fz_steps, fz_pool, osd_out, streamraw, streamstate,
         synthtx, synthoff, synthfirst, synthckpt, synthrows, audiopcm,   // K8: transmission list, offsets, first indices, phase checkpoints; wspr_selftest()'s rows; K12: one record of wspr_audio_to_iq()
-        synthfade;   // K13: one FadeChannel per transmission
+        synthfade,   // K13: one FadeChannel per transmission
+        blankrows, blankcount;   // K15: at most Context::kBlankChunk blanked records on their way to K12; one counter per record
     PinBuf h_npk, h_cand, h_items, h_sync, h_sym, h_rms, h_jobs, h_jobs2, h_seglist, h_misc, h_lists;
     // host-buffer entry (wspr_decode_batch: the reference's calling convention, wsprd.h:106-111): pageable caller rows
     // are gathered into two pinned chunks in the working layout (rows of kIqStride floats, zero tail) that take turns,

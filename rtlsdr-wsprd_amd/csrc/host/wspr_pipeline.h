@@ -234,6 +234,14 @@ public:
     // K12 (k12_audio.hip): nseg validated records of 16-bit audio resident on the device into IQ rows; complete on return
     int audio_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, float* dI, float* dQ, int normalise);
     int16_t* audio_pcm(size_t nsamp);   // device scratch for one record (wspr_audio_to_iq)
+    // K15 (k15_blank.hip): nseg validated records into blanked records; h_blanked (nseg, may be null) = samples blanked of
+    // each; complete on return
+    int audio_blank_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, void* d_out,
+                           size_t out_stride, int* h_blanked);
+    // K15 then K12 through the context's own scratch rows, kBlankChunk records at a time; complete on return
+    static constexpr int kBlankChunk = 128;
+    int audio_blanked_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, float* dI,
+                             float* dQ, int normalise, int* h_blanked);
 
     // K8 (wspr_capi_synth.hip): a validated, sorted transmission list into nseg device rows; complete on return
     // fade: one FadeChannel (kernels/fade.h) per transmission in host memory for the fading channel (K13), or null (K8)

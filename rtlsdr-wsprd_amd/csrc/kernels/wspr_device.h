@@ -268,6 +268,12 @@ void launch_decimate(const uint8_t* raw, size_t bytes_per_seg, int nseg, float* 
 // into rows of kIqStride floats, the whole row written (zero from min(ceil(nsamp / 32), 45000) on).
 void launch_audio_front(const int16_t* pcm, size_t pcm_stride, int nsamp, int nseg, float* dI, float* dQ, hipStream_t st);
 void audio_front_taps(float* gi511, float* gq511);                  // the two tap tables of audio_front.h as floats
+// K15, the impulse-noise blanker in front of K12 (k15_blank.hip; the definition in audio_blank.h): nseg records of nsamp
+// samples (rows as for K12) into rows of out_stride samples (out 16-byte aligned, out_stride a multiple of 8 and >= nsamp,
+// no overlap with the input): columns 0 .. roundup8(nsamp) - 1 written, the rest left alone.  thr16 = 16 .. 4096,
+// guard = 0 .. 64.  n_blanked: one device counter per record, ADDED to (the caller zeroes it).
+void launch_audio_blank(const int16_t* pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, int16_t* out,
+                        size_t out_stride, int* n_blanked, hipStream_t st);
 // K14, list decoding against known messages (k14_list.hip; the definition in listmatch.h): vector i = the 162 soft symbols at
 // symbols + offsets[i] * 162 (transmission order) against the m listed code words.  table: 48 x padded(m) words of four int8
 // chips, word-major, zero beyond position 161 and beyond entry m - 1; bias: B of each entry.  ListMatch is wspr_list_match
