@@ -285,6 +285,72 @@ int wspr_audio_blanked_batch_device(const void *d_pcm, size_t pcm_stride, int ns
 int wspr_audio_to_iq_blanked(const int16_t *pcm, size_t nsamp, int thr16, int guard, float *I, float *Q,
                              uint32_t *n_out, int normalise, int *n_blanked);
 
+/* ---- band noise figures per segment (K16) --------------------------------------------------------------------------
+ * What a receiver farm logs per two-minute slot and band besides the spots (wsprdaemon-style noise graphs): an "RMS" figure
+ * taken in the gaps before and after the transmissions, and an "FFT" figure, the mean of the quietest 30 % of the averaged
+ * spectrum.  The reference has no such output (its noise_level, wsprd.c:590-616, is internal, taken on a smoothed +-150 Hz
+ * spectrum, and only enters the SNR), so the definition is this library's own (rtlsdr-wsprd_amd/csrc/kernels/noise.h;
+ * tests/helpers/noise_check.c is its serial form, and the kernel equals it bit for bit).
+ * For one row of np samples (0 .. 45 000) of I and Q at 375 samples per second:
+ *   guard     if any I[k] or Q[k], k < np, has exponent bits 0xff (NaN, +Inf, -Inf; an integer test on the bit pattern), every
+ *             float of the record is 0 and flags = WSPR_NOISE_NONFINITE alone (nframes is still reported).
+ *   gaps      block b = samples 16b .. 16b+15 (42.7 ms, the stand-in for sox's 50 ms trough window);  p[b] = (float)(S / 16.0),
+ *             S the double sum, in sample order from 0.0, of (double)I*(double)I + (double)Q*(double)Q, unfused.  A window is
+ *             a block range [b0, b1), 0 <= b0 <= b1 <= 2812, clipped to the blocks wholly inside [0, np).  mean = (float)(the
+ *             double sum of (double)p[b] in rising b / the block count);  trough = the minimum p[b] ("if (p < m) m = p" from
+ *             the first block).  An empty window (after clipping as well) gives 0 for both and leaves its flag bit clear.
+ *             The two windows are arguments, not state.  wspr_noise_default_windows(): blocks 6 .. 41 (0.26 - 1.79 s) and
+ *             2672 .. 2789 (114.0 - 119.0 s) -- wsprdaemon's 0.25 - 0.75 s and 113 - 118 s moved by one second, because in
+ *             this library's rows a transmission with dt = 0 starts at 2.0 s (wspr_selftest(): dt = t0 - 2.0), not at 1.0 s.
+ *   spectrum  frames of 512 samples at hop 256: nframes = np >= 512 ? (np - 512)/256 + 1 : 0 (174 for a full row).  Window
+ *             w[n] = (float)(0.5 - 0.5*cos(2 pi n/512)), twiddles (float)cos, (float)(-sin) of 2 pi m/512, from the host libm
+ *             in double.  x = (I*w, Q*w) as float products; 512-point complex float32 radix-2 decimation-in-frequency
+ *             transform, nine stages with the butterfly of the Doppler-spread figure above, no fused multiply-add.
+ *             P_f[j] = re*re + im*im in float, separately rounded; signed bin j = -256 .. 255 lies at j * 375/512 Hz.
+ *             A[j] = the double sum of (double)P_f[j] over the frames IN THIS ORDER: four partial sums S_c[j], c = 0 .. 3, over
+ *             the frames f = c, c+4, c+8, ... in rising f from 0.0, then A[j] = ((S_0[j] + S_1[j]) + S_2[j]) + S_3[j].
+ *             a[j] = (float)(A[j] / (double)nframes / W2), W2 = the double sum of (double)w[n]*(double)w[n] in rising n: white
+ *             noise of per-rail variance s^2 gives E a[j] = 2 s^2, the scale of the gap figure.
+ *             The 443 bins j = -221 .. 221 (+-161.9 Hz: 1338 .. 1662 Hz of the audio world) are ranked by their uint32 bit
+ *             pattern (finite and >= +0: the numeric order), ties to the lower j.  fft_floor = (float)(the double sum of the
+ *             132 lowest in rank order / 132.0), the quietest 30 %; fft_p30 = the value of rank 132.  nframes == 0 gives 0
+ *             for both and leaves the flag bit clear.
+ *   flags     bit 0 pre window used, bit 1 post window used, bit 2 spectrum used, bit 3 WSPR_NOISE_NONFINITE.
+ * UNITS.  All powers are linear, per complex sample, relative to the row's own scale; dB is 10*log10() on the caller's side.
+ * THE FIGURES ARE UNCALIBRATED, and meaningless in absolute terms on a row that was normalised to a peak of 0.5: noise
+ * logging wants the normalise = 0 rows of wspr_audio_batch_device() / wspr_decimate_u8_batch_device().
+ * wspr_set_arithmetic() does not touch this stage, and no decode call runs it.
+ * What to expect: on white noise the gap means are unbiased (2 s^2); fft_floor, the mean of the lowest 30 % of 443 averaged
+ * bins, reads 0.911 of 2 s^2 (-0.41 dB) with a row-to-row standard deviation of 0.0061, and fft_p30 0.957 +- 0.0062
+ * (MEASURED on 2 048 rows of the synthesiser's noise on an MI355X, profiles/noise_figure.json; 0.912 +- 0.0059 on 64 rows of
+ * numpy's noise through the serial checker): an order-statistics bias of the estimator, not of the band.  The troughs read
+ * 0.55 +- 0.08 (36 blocks) and 0.48 +- 0.06 (118 blocks) of 2 s^2: the minimum of that many block powers.  Ten strong
+ * signals in the band (+0 .. +9 dB) raise fft_floor by 0.47 dB; stations that start up to a second early fill the pre window
+ * (pre_mean +10.8 dB in that scene) while its trough moves by 0.05 dB in the median.
+ *
+ * wspr_noise_batch_device(): nseg rows resident on the device (row s at d_idat + s*seg_stride floats; rows 16-byte aligned,
+ * seg_stride a multiple of 4 and >= samples; nothing at or behind `samples` is read) -> out[0 .. nseg) in HOST memory.
+ * w == NULL takes the default windows.  Returns 0; -1 with a line on stderr and NOTHING WRITTEN for: no device, nseg < 0 or
+ * samples < 0, rows that are not 16-byte aligned or a stride that is no multiple of 4 floats, seg_stride < samples, a window
+ * outside 0 <= b0 <= b1 <= 2812; -2 (nothing written) for samples > 45000.  nseg == 0 does nothing; samples == 0 writes
+ * records of zeros with flags = 0.  Stream contract, lane turn and scratch ownership as wspr_audio_batch_device(); the
+ * scratch (32 bytes per segment, one table of 4 KB) is returned by wspr_release_buffers().
+ * wspr_noise(): one row from host memory (any alignment), otherwise the same.
+ * (In C the record is `struct wspr_noise`: the tag shares its name with the one-row call.) */
+#define WSPR_NOISE_PRE_USED   1
+#define WSPR_NOISE_POST_USED  2
+#define WSPR_NOISE_FFT_USED   4
+#define WSPR_NOISE_NONFINITE  8
+typedef struct { int32_t pre_b0, pre_b1, post_b0, post_b1; } wspr_noise_windows;
+struct wspr_noise {                 /* 32 bytes */
+    float   pre_mean, pre_trough, post_mean, post_trough, fft_floor, fft_p30;
+    int32_t nframes, flags;
+};
+void wspr_noise_default_windows(wspr_noise_windows *w);
+int wspr_noise_batch_device(const void *d_idat, const void *d_qdat, int nseg, int samples, size_t seg_stride,
+                            const wspr_noise_windows *w /* NULL = default */, struct wspr_noise *out /* host, nseg */);
+int wspr_noise(const float *I, const float *Q, int samples, const wspr_noise_windows *w, struct wspr_noise *out);
+
 /* ---- signal synthesiser (K8) ------------------------------------------------------------------------------
  * The reference's self-test generator (decoderSelfTest() / whiteGaussianNoise(), rtlsdr_wsprd.c:706-760) for batches
  * of scenes resident in HBM: from "symbols, frequency, time, level" to the IQ rows wspr_decode_batch_device() takes,

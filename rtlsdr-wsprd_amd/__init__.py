@@ -180,6 +180,12 @@ def _bind(path):
     L.wspr_audio_to_iq_blanked.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_int, C.c_void_p]
     L.wspr_audio_to_iq_blanked.restype = C.c_int
+    L.wspr_noise_default_windows.argtypes = [C.c_void_p]
+    L.wspr_noise_default_windows.restype = None
+    L.wspr_noise_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]
+    L.wspr_noise_batch_device.restype = C.c_int
+    L.wspr_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.wspr_noise.restype = C.c_int
     L.wspr_read_wav_file.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
     L.wspr_read_wav_file.restype = C.c_size_t
     L.wspr_selftest.argtypes = [decoder_options, C.c_void_p]
@@ -530,6 +536,61 @@ def audio_to_iq_blanked(pcm, thr16, guard, normalise=0):
         raise RuntimeError("wspr_audio_to_iq_blanked failed (rc %d: settings out of range, a record above 120 s, or no usable "
                            "HIP device)" % rc)
     return I, Q, int(n_out.value), int(n_blanked.value)
+
+
+# include/wspr_mi355x.h: wspr_noise_windows and struct wspr_noise, the band noise figures of a segment (K16)
+NOISE_WINDOWS_DTYPE = np.dtype([("pre_b0", "<i4"), ("pre_b1", "<i4"), ("post_b0", "<i4"), ("post_b1", "<i4")])
+NOISE_DTYPE = np.dtype([("pre_mean", "<f4"), ("pre_trough", "<f4"), ("post_mean", "<f4"), ("post_trough", "<f4"),
+                        ("fft_floor", "<f4"), ("fft_p30", "<f4"), ("nframes", "<i4"), ("flags", "<i4")])
+NOISE_PRE_USED, NOISE_POST_USED, NOISE_FFT_USED, NOISE_NONFINITE = 1, 2, 4, 8
+NOISE_MAX_BLOCK = 2812
+
+
+def _noise_windows(windows):
+    """None (the library's default) or (pre_b0, pre_b1, post_b0, post_b1) as what the call takes."""
+    if windows is None:
+        return None, None
+    w = np.array([tuple(int(x) for x in windows)], NOISE_WINDOWS_DTYPE)
+    return w, _ptr(w)
+
+
+def noise_default_windows():
+    """wspr_noise_default_windows(): (pre_b0, pre_b1, post_b0, post_b1) in blocks of 16 samples.  Needs no device."""
+    w = np.zeros(1, NOISE_WINDOWS_DTYPE)
+    lib().wspr_noise_default_windows(_ptr(w))
+    return tuple(int(x) for x in w[0])
+
+
+def noise_batch_device(d_i, d_q, nseg, samples, seg_stride, windows=None, out=None):
+    """wspr_noise_batch_device(): the band noise figures (K16) of nseg rows at the raw device pointers d_i / d_q (16-byte
+    aligned, seg_stride floats apart).  The figures are UNCALIBRATED linear powers relative to the row's scale: log them
+    from rows that were not normalised.  out: a NOISE_DTYPE array of nseg to write into, or None.  Returns (rc, records):
+    rc is the library's code (0; -1 or -2 with nothing written)."""
+    if out is None:
+        out = np.zeros(max(int(nseg), 0), NOISE_DTYPE)
+    keep, w = _noise_windows(windows)
+    rc = lib().wspr_noise_batch_device(d_i, d_q, int(nseg), int(samples), int(seg_stride), w, _ptr(out))
+    return rc, out
+
+
+def noise(I, Q, windows=None, samples=None):
+    """wspr_noise(): the figures of one host row as a NOISE_DTYPE record; raises if the library refuses the call."""
+    I = np.ascontiguousarray(I, dtype=np.float32)
+    Q = np.ascontiguousarray(Q, dtype=np.float32)
+    out = np.zeros(1, NOISE_DTYPE)
+    keep, w = _noise_windows(windows)
+    rc = lib().wspr_noise(_ptr(I), _ptr(Q), int(I.size if samples is None else samples), w, _ptr(out))
+    if rc != 0:
+        raise RuntimeError("wspr_noise failed (rc %d: a window out of range, more than 45000 samples, or no usable HIP "
+                           "device)" % rc)
+    return out[0]
+
+
+def to_db(power):
+    """10 log10 of a linear figure (a scalar or an array); 0 and below give -inf.  Still uncalibrated."""
+    p = np.asarray(power, np.float64)
+    with np.errstate(divide="ignore"):
+        return np.where(p > 0.0, 10.0 * np.log10(np.where(p > 0.0, p, 1.0)), -np.inf)
 
 
 def read_wav_file(filename, cap=AUDIO_MAX_SAMPLES):

@@ -4,6 +4,7 @@
 // reference's sync_and_demodulate() / subtract_signal*().  The decode is wspr_pipeline.hip.
 #include "wspr_context_impl.h"
 #include "../kernels/glibc_sincosf.h"
+#include "../kernels/noise.h"
 
 namespace wspr {
 
@@ -194,10 +195,10 @@ size_t Context::release_buffers() {
                               &c.lists, &c.scrsync, &c.psavg, &c.densein, &c.fz_sym, &c.fz_off, &c.fz_ret, &c.fz_cyc, &c.fz_met, &c.fz_max,
                               &c.fz_dat, &c.fz_steps, &c.fz_pool, &c.streamraw, &c.streamstate, &c.synthtx, &c.synthoff, &c.synthfirst,
                               &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out, &c.spr_tw, &c.spr_jobs, &c.spr_ckpt, &c.spr_out, &c.audiopcm, &c.synthfade, &c.list_out,
-                              &c.blankrows, &c.blankcount})
+                              &c.blankrows, &c.blankcount, &c.noise_tab, &c.noise_out})
                 freed += b->release();
             for (PinBuf* b : {&c.h_npk, &c.h_cand, &c.h_items, &c.h_sync, &c.h_sym, &c.h_rms, &c.h_jobs, &c.h_jobs2, &c.h_seglist,
-                              &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_sprjobs, &c.h_sprout, &c.h_list, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
+                              &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_sprjobs, &c.h_sprout, &c.h_noise, &c.h_list, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
                 b->release();
             c.stage_samples[0] = c.stage_samples[1] = 0;
             free(c.hash_arena);
@@ -721,6 +722,35 @@ int Context::audio_blanked_device(const void* d_pcm, size_t pcm_stride, int nsam
     } else {
         HIP_OK(hipStreamSynchronize(c.stream));
     }
+    return 0;
+}
+
+// K16 on the lane's stream; the records come back with it.  The table is built on first use: a process that never asks
+// for the figures allocates nothing for them.
+int Context::noise_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, const noise::Windows& win,
+                          noise::Result* out) {
+    Impl& c = *d;
+    if (nseg <= 0) return 0;
+    if (!c.noise_tab.p) {
+        std::vector<float> host(noise::kTableFloats);
+        const double w2 = noise::noise_tables(host.data());
+        float* p = static_cast<float*>(c.noise_tab.need(host.size() * sizeof(float)));
+        HIP_OK(hipMemcpy(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+        c.noise_w2 = w2;
+    }
+    const size_t bytes = (size_t)nseg * sizeof(noise::Result);
+    void* d_out = c.noise_out.need(bytes);
+    noise::Result* h_out = static_cast<noise::Result*>(c.h_noise.need(bytes));
+    launch_noise(dI, dQ, samples, stride, nseg, c.noise_tab.as<float>(), c.noise_w2, win, d_out, c.stream);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h_out, d_out, bytes, hipMemcpyDeviceToHost, c.stream));
+    if (c.blocking) {
+        HIP_OK(hipEventRecord(c.ev_sync, c.stream));
+        host_wait(c.ev_sync);
+    } else {
+        HIP_OK(hipStreamSynchronize(c.stream));
+    }
+    memcpy(out, h_out, bytes);                               // every record has arrived before the first is handed over
     return 0;
 }
 

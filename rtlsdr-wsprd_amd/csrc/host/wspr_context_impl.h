@@ -248,7 +248,9 @@ struct Context::Impl {
         nvalid, decscratch, tabs, pw, pwfreq, lagprune, lists, scrsync, psavg, densein, fz_sym, fz_off, fz_ret, fz_cyc, fz_met, fz_max, fz_dat, fz_steps, fz_pool, osd_out, streamraw, streamstate,
         synthtx, synthoff, synthfirst, synthckpt, synthrows, audiopcm,   // K8: transmission list, offsets, first indices, phase checkpoints; wspr_selftest()'s rows; K12: one record of wspr_audio_to_iq()
         synthfade,   // K13: one FadeChannel per transmission
-        blankrows, blankcount;   // K15: at most Context::kBlankChunk blanked records on their way to K12; one counter per record
+        blankrows, blankcount,   // K15: at most Context::kBlankChunk blanked records on their way to K12; one counter per record
+        noise_tab, noise_out;    // K16: twiddles and window (built on first use); one 32-byte record per segment
+    double noise_w2 = 0.0;       // K16: the sum of the squared window, from the same pass as the table
     PinBuf h_npk, h_cand, h_items, h_sync, h_sym, h_rms, h_jobs, h_jobs2, h_seglist, h_misc, h_lists;
     // host-buffer entry (wspr_decode_batch: the reference's calling convention, wsprd.h:106-111): pageable caller rows
     // are gathered into two pinned chunks in the working layout (rows of kIqStride floats, zero tail) that take turns,
@@ -263,6 +265,7 @@ struct Context::Impl {
     PinBuf h_blk;                    // ... on their way to the host
     DevBuf spr_tw, spr_jobs, spr_ckpt, spr_out;   // K11: twiddles (built on first use), jobs, phase checkpoints, 4 words per job
     PinBuf h_sprjobs, h_sprout;      // ... the jobs on their way up, the results on their way down
+    PinBuf h_noise;                  // K16: the records on their way down
     wspr_spread* spread_out = nullptr;   // where the current call's records go (the layout of its `decodes`), or null
     PinBuf h_stage[2];
     PinBuf h_streamraw, h_streamstate, h_streamout;   // many receivers' callbacks at once (decimate_stream_many)

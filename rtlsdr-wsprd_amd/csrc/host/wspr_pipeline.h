@@ -243,6 +243,11 @@ public:
     int audio_blanked_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, float* dI,
                              float* dQ, int normalise, int* h_blanked);
 
+    // K16 (k16_noise.hip; the definition in kernels/noise.h): the noise figures of nseg validated device rows into out (host,
+    // nseg records); complete on return.  The table of twiddles and window is built on first use, as spread_twiddle_table().
+    int noise_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, const noise::Windows& win,
+                     noise::Result* out);
+
     // K8 (wspr_capi_synth.hip): a validated, sorted transmission list into nseg device rows; complete on return
     // fade: one FadeChannel (kernels/fade.h) per transmission in host memory for the fading channel (K13), or null (K8)
     int synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, float sigma, uint64_t seed,

@@ -274,6 +274,13 @@ void audio_front_taps(float* gi511, float* gq511);                  // the two t
 // guard = 0 .. 64.  n_blanked: one device counter per record, ADDED to (the caller zeroes it).
 void launch_audio_blank(const int16_t* pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, int16_t* out,
                         size_t out_stride, int* n_blanked, hipStream_t st);
+// K16, the band noise figures of a segment (k16_noise.hip; the definition in noise.h): nseg rows of `samples` samples
+// (0 .. kMaxSamples; rows 16-byte aligned, stride a multiple of 4 floats and >= samples; nothing at or behind `samples` is
+// read) into nseg records of 32 bytes (noise::Result) at out.  table: noise::kTableFloats floats of noise::noise_tables(),
+// w2 its return value; win: validated windows.
+namespace noise { struct Windows; struct Result; }
+void launch_noise(const float* dI, const float* dQ, int samples, size_t stride, int nseg, const float* table, double w2,
+                  const noise::Windows& win, void* out, hipStream_t st);
 // K14, list decoding against known messages (k14_list.hip; the definition in listmatch.h): vector i = the 162 soft symbols at
 // symbols + offsets[i] * 162 (transmission order) against the m listed code words.  table: 48 x padded(m) words of four int8
 // chips, word-major, zero beyond position 161 and beyond entry m - 1; bias: B of each entry.  ListMatch is wspr_list_match
