@@ -138,17 +138,19 @@ void launch_demod(const float* dI, const float* dQ, int samples, const FineState
 // item indices without / with drift.  mode 0: nlag lags shift_coarse-128 + lagstep*m;
 // mode 2: 43 lags shift-63+3*m (lagstep must be 3).  pw: nitems*nlag*162 float4 of scratch.
 void launch_phasor_tables(const FineState* items, int nitems, int mode, float* tabs, hipStream_t st, int arith);
-// Lag pruning of the full mode-0 scan (33 lags, step 8; k4_demod.hip): a cheap bounded pass names the lags that can still
+// Lag pruning of the full mode-0 scan (33 lags, step 8; k4_lag_prune.h, launched from k4_demod.hip): a cheap bounded pass names the lags that can still
 // win, exact sums are formed for those only.  The caller provides `scratch` (lag_prune_scratch_bytes(nitems) bytes) and
 // `counts`, three ints of device memory it has zeroed: [0] exact single-lag evaluations, [1] candidates that fell back
 // to the whole scan, [2] candidates pruned; launch_demod_tiled() sets `mask` (per item, bit m = lag m was summed; null
 // when it did not prune) for launch_pick_lag().  `audit` (null everywhere but in tools/lagprune_check.hip): nitems x 33 x 7
 // floats of device memory that receive the coarse pass' own numbers per (item, lag) -- sync~, eps, totp~, ss~, T~, delta_tab,
-// flagged bad (1.0f / 0.0f) -- for the drift-free candidates; see the pruning block of k4_demod.hip.
-// `drift` (opt-in; the decode pipeline sets it): the drifting candidates are pruned as well, by kernels of their own
-// (lag_coarse_drift_kernel ...).  `counts` is then EIGHT zeroed ints: [4] exact single-lag evaluations, [5] fallbacks and
+// flagged bad (1.0f / 0.0f) -- for the drift-free candidates; see k4_lag_prune.h.
+// `drift` (opt-in; the decode pipeline sets it): the drifting candidates are pruned as well: a coarse pass of their own
+// (lag_coarse_drift_kernel + lag_coarse_drift_fold_kernel), then the same contender stage (lp_decide) and the same exact
+// kernel (lag_exact_kernel<., true>).  `counts` is then EIGHT zeroed ints: [4] exact single-lag evaluations, [5] fallbacks and
 // [6] candidates pruned among the drifting ones; their lists follow the drift-free ones in `scratch`, and `audit` receives
-// their rows too.  A drifting candidate that falls back takes demod_drift_kernel's whole scan.  Off: drifting candidates take the whole scan, mask all ones, counts[4..] and the rest of scratch untouched.
+// their rows too.  A drifting candidate that falls back takes demod_drift_kernel's whole scan (<., true>: over the fallback
+// list).  Off: drifting candidates take the whole scan, mask all ones, counts[4..] and the rest of scratch untouched.
 struct LagPrune {
     void* scratch;
     int* counts;

@@ -145,8 +145,8 @@ def tool():
     exe = os.path.join(ROOT, "tools", "fine_check.bin")
     src = os.path.join(ROOT, "tools", "fine_check.hip")
     kern = os.path.join(ROOT, "rtlsdr-wsprd_amd", "csrc", "kernels")
-    newest = max(os.path.getmtime(p) for p in (src, os.path.join(kern, "k4_demod.hip"), os.path.join(kern, "wspr_device.h"),
-                                               os.path.join(kern, "demod_math.h")))
+    newest = max(os.path.getmtime(p) for p in (src, os.path.join(kern, "k4_demod.hip"), os.path.join(kern, "k4_lag_prune.h"),
+                                               os.path.join(kern, "wspr_device.h"), os.path.join(kern, "demod_math.h")))
     if not os.path.exists(exe) or os.path.getmtime(exe) < newest:
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
                         "-fno-fast-math", "-I", kern, src, "-o", exe], check=True, capture_output=True)

@@ -1,5 +1,5 @@
 """CPU side of the coarse-kernel audit (tests/test_gpu_lag_coarse.py, tests/test_lag_audit_cpu.py): the float64 references
-of what lag_coarse_kernel computes (k4_demod.hip; DESIGN.md section 4 "The bound of the lag pruning"), the bound restated
+of what lag_coarse_kernel computes (k4_lag_prune.h; DESIGN.md section 4 "The bound of the lag pruning"), the bound restated
 from the kernel's own audit numbers, the contender rule in float32, and the case / output files of tools/lagprune_check.hip.
 The kernel's pass in numpy (coarse_pass), the oracle's single-lag sync and the candidates are those of
 tests/test_lag_bound_cpu.py.  TEST INFRASTRUCTURE ONLY."""
@@ -186,12 +186,11 @@ def fallback_cases():
 def tool():
     exe = os.path.join(ROOT, "tools", "lagprune_check.bin")
     src = os.path.join(ROOT, "tools", "lagprune_check.hip")
-    newest = max(os.path.getmtime(p) for p in (src, os.path.join(ROOT, "rtlsdr-wsprd_amd", "csrc", "kernels", "k4_demod.hip"),
-                                               os.path.join(ROOT, "rtlsdr-wsprd_amd", "csrc", "kernels", "wspr_device.h")))
-    if not os.path.exists(exe) or os.path.getmtime(exe) < newest:
+    kern = os.path.join(ROOT, "rtlsdr-wsprd_amd", "csrc", "kernels")
+    newest = max(os.path.getmtime(os.path.join(kern, f)) for f in ("k4_demod.hip", "k4_lag_prune.h", "wspr_device.h"))
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(newest, os.path.getmtime(src)):
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                        "-fno-fast-math", "-I", os.path.join(ROOT, "rtlsdr-wsprd_amd", "csrc", "kernels"), src, "-o", exe],
-                       check=True, capture_output=True)
+                        "-fno-fast-math", "-I", kern, src, "-o", exe], check=True, capture_output=True)
     return exe
 
 

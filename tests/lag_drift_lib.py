@@ -1,4 +1,4 @@
-"""CPU side of the lag pruning of DRIFTING candidates (k4_demod.hip: lag_coarse_drift_kernel and its fold kernel; DESIGN.md
+"""CPU side of the lag pruning of DRIFTING candidates (k4_lag_prune.h: lag_coarse_drift_kernel and its fold kernel; DESIGN.md
 section 4 "The bound for drifting candidates"): the coarse pass at one frequency per symbol restated in numpy, the a priori bound
 delta_{s,t} on the reference's float phasor recurrence, the oracle's single-lag sync of a drifting candidate, and the case sets of
 tests/test_lag_bound_drift_cpu.py and the GPU tests.  The constants are those of tests/test_lag_bound_cpu.py.

@@ -1,4 +1,4 @@
-"""lag_coarse_kernel (k4_demod.hip) held to the quantities the proof of DESIGN.md section 4 "The bound of the lag pruning" talks
+"""lag_coarse_kernel (k4_lag_prune.h) held to the quantities the proof of DESIGN.md section 4 "The bound of the lag pruning" talks
 about.  tools/lagprune_check.hip runs the production launchers on a case file -- A: the pruned scan with the kernel's audit
 output (per item and lag: sy, ep, totp, ss, tm, dtab, bad), B: the whole scan -- and dumps every buffer; the references are
 float64 numpy (tests/lag_audit_lib.py), the oracle's single-lag sync in the exact mode and the CONTRACT=1 checker's

@@ -1,4 +1,4 @@
-"""lag_coarse_drift_kernel and its fold kernel (k4_demod.hip) held to the quantities the proof of DESIGN.md section 4 talks about:
+"""lag_coarse_drift_kernel and its fold kernel (k4_lag_prune.h) held to the quantities the proof of DESIGN.md section 4 talks about:
 tests/test_gpu_lag_coarse.py's seven assertions, transposed to the DRIFTING items of a list.  tools/lagprune_check.hip with its
 "drift" option runs the production launchers with LagPrune::drift on -- A: the pruned scan with the audit output, B: the whole
 scan (demod_drift_kernel) -- and dumps every buffer.  Per drifting item and lag, check_run() asserts:

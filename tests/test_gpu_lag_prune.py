@@ -1,4 +1,4 @@
-"""The lag pruning of the fine search's mode-0 scan (k4_demod.hip: lag_coarse_kernel picks the lags that can still win,
+"""The lag pruning of the fine search's mode-0 scan (k4_lag_prune.h: lag_coarse_kernel picks the lags that can still win,
 lag_exact_kernel sums those, the whole strided scan is the fallback) must leave every candidate's mode-0 result -- and
 with it everything downstream -- what the oracle computes: all of it through wspr_decode_batch_trace() and
 trace_parity.check, on inputs made to reach the corners of the new path.  The counts come from the LAB library's

@@ -1,5 +1,5 @@
-"""The lag pruning of DRIFTING candidates in the decode pipeline (k4_demod.hip: lag_coarse_drift_kernel names the lags that can
-still win, lag_exact_drift_kernel sums those, demod_drift_list_kernel, demod_drift_kernel's whole scan over the fallback list, is the fallback) must leave every candidate's mode-0 result --
+"""The lag pruning of DRIFTING candidates in the decode pipeline (k4_lag_prune.h: lag_coarse_drift_kernel names the lags that can
+still win, lag_exact_kernel<., true> sums those, demod_drift_kernel<., true>, the whole scan over the fallback list, is the fallback) must leave every candidate's mode-0 result --
 and with it everything downstream -- what the oracle computes: through wspr_decode_batch_trace() and trace_parity.check, as
 tests/test_gpu_lag_prune.py does for the drift-free candidates.  The counts come from the LAB library's wspr_last_timings():
 [41] drifting candidates pruned, [42] their exact single-lag evaluations, [43] their fallbacks; [29]..[31] keep counting the

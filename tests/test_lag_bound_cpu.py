@@ -1,4 +1,4 @@
-"""The bound of the lag pruning (k4_demod.hip: lag_coarse_kernel; DESIGN.md section 4 "The bound of the lag pruning"), restated in
+"""The bound of the lag pruning (k4_lag_prune.h: lag_coarse_kernel; DESIGN.md section 4 "The bound of the lag pruning"), restated in
 numpy and held against the oracle's own sync of every single lag: for a drift-free candidate the sync of lag m formed
 from sliding block sums of ONE mixed-down stream per tone differs from the reference's by at most eps(m), and the lag
 the reference picks is therefore among the contenders.  The constants are the derivation's, not tuned to this data;
@@ -20,7 +20,7 @@ _libm = C.CDLL("libm.so.6")
 for _f in (_libm.sinf, _libm.cosf):
     _f.argtypes, _f.restype = [C.c_float], C.c_float
 
-# ---- the derivation's constants (kLp* of k4_demod.hip) ----
+# ---- the derivation's constants (kLp* of k4_lag_prune.h) ----
 U = 2.0 ** -24
 GAMMA_REF = 514 * U / (1 - 514 * U)              # (a) the reference's serial sum: 514 roundings per term
 COARSE = 64 * U                                  # (c) the coarse pass' own rounding

@@ -1,4 +1,4 @@
-"""The bound of the lag pruning of DRIFTING candidates (k4_demod.hip: lag_coarse_drift_kernel; DESIGN.md section 4 "The bound for
+"""The bound of the lag pruning of DRIFTING candidates (k4_lag_prune.h: lag_coarse_drift_kernel; DESIGN.md section 4 "The bound for
 drifting candidates"), restated in numpy (tests/lag_drift_lib.py) and held against the oracle's own sync of every single lag:
 (a) soundness -- |exact - coarse| <= eps on every lag, the reference's pick among the contenders, and the a priori bound on the
 float phasor recurrence above what the recurrence does over the whole range of frequencies and drifts; (b) the caps -- on the

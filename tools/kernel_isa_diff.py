@@ -24,7 +24,18 @@ SOURCES = ("k1_fft_bank", "k4_demod", "k7_subtract")
 META = ("vgpr_count", "sgpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count")
 # the exact instantiations of the kernels that each take >= 5 % of a configs[2] step (profiles/contracted_ab.txt)
 GATED = ("sub_fir_fused_kernel<false>", "demod_lagsys_kernel<false>", "freq_scalar_kernel<false>",
-         "demod_drift_kernel<false>", "freq_drift_kernel<false>")
+         "demod_drift_kernel<false, false>", "freq_drift_kernel<false>")
+# instantiations that a refactor renamed (base tree's name -> new tree's): compared with each other, under the new name
+RENAMED = {
+    "demod_drift_kernel<false>": "demod_drift_kernel<false, false>",
+    "demod_drift_kernel<true>": "demod_drift_kernel<true, false>",
+    "demod_drift_list_kernel<false>": "demod_drift_kernel<false, true>",
+    "demod_drift_list_kernel<true>": "demod_drift_kernel<true, true>",
+    "lag_exact_kernel<false>": "lag_exact_kernel<false, false>",
+    "lag_exact_kernel<true>": "lag_exact_kernel<true, false>",
+    "lag_exact_drift_kernel<false>": "lag_exact_kernel<false, true>",
+    "lag_exact_drift_kernel<true>": "lag_exact_kernel<true, true>",
+}
 
 
 def build_flags(tree):
@@ -105,6 +116,7 @@ def main():
     for v, (variant, extra) in enumerate(variants):
         for src in SOURCES:
             base, new = asm[(a.base, src, v)], asm[(a.new, src, v)]
+            base = {(RENAMED[k] if RENAMED.get(k) in new else k): f for k, f in base.items()}
             diffs = compare(base, new)
             rep.append("%s, %s.hip: %d functions in the base tree, %d in the new one, %d differ" % (
                 variant, src, len(base), len(new), len(diffs)))

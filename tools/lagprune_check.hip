@@ -12,7 +12,7 @@
 // exact list: 4 n_shared ints, fallback list: n_shared ints); int32 counts[4]; float audit[nitems][33][7].
 // With a third argument "drift" the pruned run also prunes the drifting candidates (LagPrune::drift) and every run's dump
 // ends with int32 counts[4..7] (drifting candidates: exact evaluations, fallbacks, pruned, unused); their lists are in the
-// scratch dump behind the drift-free ones (lag_prune_scratch_bytes() in k4_demod.hip gives the layout).
+// scratch dump behind the drift-free ones (lag_prune_scratch_bytes() in k4_lag_prune.h gives the layout).
 // Every output buffer starts as bytes of 0xa5 (as a float: -2.87e-16), so what no kernel wrote can be told.
 #include "../rtlsdr-wsprd_amd/csrc/kernels/k4_demod.hip"
 #include <cstdio>
