@@ -456,6 +456,55 @@ int wspr_synth_faded_batch_device(const wspr_synth_tx *tx, const wspr_synth_chan
 int wspr_synth_faded(const wspr_synth_tx *tx, const wspr_synth_channel *ch, int ntx, float noise_sigma,
                      uint64_t seed, int flags, float *I, float *Q);
 
+/* ---- 12 kHz audio scene synthesiser (K17) ---------------------------------------------------------------------
+ * The synthesiser above for the AUDIO path: from "symbols, frequency, time, level, drift" to the 16-bit records
+ * wspr_audio_batch_device() and wspr_audio_blank*_batch_device() take -- 12 000 samples per second, the band centred on
+ * 1 500 Hz, 8 192 samples per symbol.  It is also the transmit side: get_wspr_channel_symbols(), wspr_synth_audio() and
+ * wspr_write_wav_file() turn a message into the audio a transmitter plays.  Under the contract of K8 a CPU reproduces
+ * every sample bit for bit (rtlsdr-wsprd_amd/csrc/kernels/audio_synth.h is the definition, tests/helpers/
+ * audio_synth_check.cpp its serial form).  All arithmetic is double, unfused, in the order written; sine, cosine and the
+ * Gaussian draw are those of K8 (synth_math.h).  A transmission is a wspr_synth_tx as above; here amp and noise_sigma are
+ * in PCM units (LSB).
+ *
+ * For record s of nsamp samples (0 .. 1 440 000), global segment S = seg_index0 + s, output sample k, in this order:
+ *   1. acc = 0.0, or (double)pcm[k] with WSPR_SYNTH_ACCUMULATE (the bit of wspr_synth_batch_device(): a known test signal
+ *      onto a recorded slot that is already resident in HBM).
+ *   2. If noise_sigma > 0: acc = acc + (double)n_k.  One float32 Gaussian pair (a, b) per PAIR of samples, m = k >> 1:
+ *      Philox-4x32-10 keyed by the seed, counter = (m, 0x80000000, S low, S high), through exactly the Box-Muller of K8's
+ *      noise; sample 2m takes a, sample 2m + 1 takes b.  Counter word 1 = 0x80000000 is a stream of its own (K8's noise
+ *      uses 0, K13's impulses 1 + 2q + p).  A record's noise does not depend on how a job is split.
+ *   3. For each transmission of the segment IN LIST ORDER: acc = acc + (double)amp * cos(phi), with
+ *        df = 12000.0/8192.0,  fd_i = ((double)drift/2.0) * ((double)i - 81.0)/81.0,
+ *        dphi_i = (2.0*3.14159265358979323846) * (1/12000.0) * (((1500.0 + (double)f0) + fd_i) + ((double)symbols[i] - 1.5) * df),
+ *        P_0 = 0.0,  P_{i+1} = P_i + 8192.0 * dphi_i     (162 dependent adds, run as written),
+ *        phi = P_i + (double)j * dphi_i                   for sample j = 0 .. 8191 of symbol i,
+ *      at output index k = first + 8192 i + j, first = floor((double)t0 * 12000.0) clamped to +-4 000 000 (a far-away
+ *      frame simply misses the record).  Indices outside [0, nsamp) are dropped: a frame may hang off either end.
+ *   4. acc > 32767.0 gives 32767, acc < -32768.0 gives -32768, and either counts as clipped; otherwise the sample is
+ *      (acc + 6755399441055744.0) - 6755399441055744.0 -- nearest, ties to even -- as an int16.  n_clipped[s] is the
+ *      record's count.
+ * RANGE: the sine and cosine are valid below 2^20 * pi/2 rad, which 1 327 104 samples reach at 2 370 Hz; 1500 + |f0| +
+ * |drift|/2 + 2.2 Hz stays below that for |f0| + |drift|/2 <= 800 Hz, and a call beyond is refused.
+ * LEVELS: real noise of standard deviation sigma at 12 kHz has power sigma^2 * 2500/6000 in 2 500 Hz, so a signal at
+ * `snr` dB in the decoder's convention has amp = sigma * sqrt(5000/6000) * 10^(snr/20).
+ *
+ * wspr_synth_audio_batch_device(): row s is at d_pcm + s*pcm_stride samples; d_pcm 16-byte aligned device memory,
+ * pcm_stride a multiple of 8 and >= nsamp.  Columns 0 .. roundup8(nsamp) - 1 are written: from nsamp on they are zero
+ * without WSPR_SYNTH_ACCUMULATE and keep what they held with it; the columns behind are left alone.  Returns 0; -1 with a
+ * line on stderr and NOTHING WRITTEN (n_clipped included) for: no device, a symbol > 3, seg outside the batch, an unsorted
+ * list, negative counts, a non-finite f0 / t0 / amp / drift / noise_sigma, noise_sigma < 0, |amp| or noise_sigma > 1e6,
+ * |f0| + |drift|/2 > 800 Hz, any flag bit other than WSPR_SYNTH_ACCUMULATE, misalignment, a stride that is no multiple of
+ * 8 or is too small; -2 for nsamp > 1 440 000.  nseg == 0 does nothing, nsamp == 0 writes no sample (n_clipped: zeros).
+ * Stream contract and lane turn as wspr_audio_batch_device(); the scratch (the list, 2 592 B of phases per transmission,
+ * one counter per record) belongs to the lane's context and is returned by wspr_release_buffers(). */
+int wspr_synth_audio_batch_device(const wspr_synth_tx *tx, int ntx, int nseg, int seg_index0, int nsamp,
+                                  float noise_sigma, uint64_t seed, int flags,
+                                  void *d_pcm, size_t pcm_stride, int *n_clipped /* host, nseg, may be NULL */);
+/* One record into host memory (read first with WSPR_SYNTH_ACCUMULATE), seg_index0 = 0: row 0 of the batch call.
+ * n_clipped: one int, may be NULL. */
+int wspr_synth_audio(const wspr_synth_tx *tx, int ntx, int nsamp, float noise_sigma, uint64_t seed, int flags,
+                     int16_t *pcm, int *n_clipped);
+
 /* ---- receiver session --------------------------------------------------------------------
  * The reference's rx_state (two I/Q buffers of 45000 samples, their fill counters, the active index,
  * rtlsdr_wsprd.c:78-90), the decimator's static state (:135-160) and the body of its decoder thread (:263-328) as
@@ -507,6 +556,9 @@ int wspr_read_c2_file(const char *filename, float *I, float *Q, double *dial_hz)
  * skipped, odd sizes padded); reads min(data samples, cap); a short data chunk yields what the file holds.
  * Returns samples read, 0 on any error or any other format.  For wspr_audio_to_iq() / wspr_audio_batch_device(). */
 size_t wspr_read_wav_file(const char *filename, int16_t *pcm, size_t cap);
+/* RIFF/WAVE writer: nsamp samples as 12 000 Hz 16-bit mono PCM, exactly what wspr_read_wav_file() reads (a record of
+ * wspr_synth_audio(), for one).  Returns 0; -1 if the file cannot be written.  Host code: needs no device. */
+int wspr_write_wav_file(const char *filename, const int16_t *pcm, size_t nsamp);
 /* Replaces writeRawIQfile(), reference rtlsdr_wsprd.c:595-617. */
 int wspr_write_iq_file(const char *filename, const float *I, const float *Q);
 /* The "Spot : ..." line of decodeRecordedFile(), reference rtlsdr_wsprd.c:691-701. */

@@ -9,6 +9,7 @@ There is NO CPU fallback: every entry point raises if the library is missing and
 the library itself refuses to run without a HIP device.
 """
 import ctypes as C
+import math
 import os
 import subprocess
 
@@ -188,6 +189,13 @@ def _bind(path):
     L.wspr_noise.restype = C.c_int
     L.wspr_read_wav_file.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
     L.wspr_read_wav_file.restype = C.c_size_t
+    L.wspr_write_wav_file.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
+    L.wspr_write_wav_file.restype = C.c_int
+    L.wspr_synth_audio_batch_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_uint64,
+                                                C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.wspr_synth_audio_batch_device.restype = C.c_int
+    L.wspr_synth_audio.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
+    L.wspr_synth_audio.restype = C.c_int
     L.wspr_selftest.argtypes = [decoder_options, C.c_void_p]
     L.wspr_selftest.restype = C.c_int
     L.nhash.restype = C.c_uint32
@@ -599,6 +607,55 @@ def read_wav_file(filename, cap=AUDIO_MAX_SAMPLES):
     pcm = np.zeros(max(1, int(cap)), np.int16)
     n = lib().wspr_read_wav_file(os.fsencode(filename), _ptr(pcm), int(cap))
     return pcm[:n].copy()
+
+
+def write_wav_file(filename, pcm):
+    """wspr_write_wav_file(): int16 samples as a 12 000 Hz 16-bit mono PCM WAV file, what read_wav_file() reads.  Raises if
+    the file cannot be written.  Host code: needs no device."""
+    pcm = np.ascontiguousarray(pcm, dtype=np.int16)
+    if lib().wspr_write_wav_file(os.fsencode(filename), _ptr(pcm), int(pcm.size)) != 0:
+        raise OSError("wspr_write_wav_file could not write %r" % (filename,))
+
+
+def audio_amp(snr_db, noise_sigma):
+    """The level convention of the audio scene synthesiser (K17): the amplitude, in PCM units, of a signal at snr_db (the
+    decoder's convention: noise power in 2 500 Hz) over real noise of standard deviation noise_sigma at 12 000 samples per
+    second, which has noise_sigma^2 * 2500/6000 of its power in those 2 500 Hz."""
+    return float(noise_sigma) * math.sqrt(5000.0 / 6000.0) * 10.0 ** (float(snr_db) / 20.0)
+
+
+def _synth_items(items):
+    """(pointer, count, keep-alive) of a transmission list: a list as for synth_tx_list(), or a SYNTH_TX_DTYPE array."""
+    if isinstance(items, np.ndarray):
+        assert items.dtype == SYNTH_TX_DTYPE and items.flags.c_contiguous
+        return items.ctypes.data, int(items.size), items
+    arr = synth_tx_list(items)
+    return C.addressof(arr), len(items), arr
+
+
+def synth_audio_batch_device(items, nseg, nsamp, d_pcm, pcm_stride, seg_index0=0, noise_sigma=0.0, seed=0, flags=0,
+                             n_clipped=None):
+    """wspr_synth_audio_batch_device(): the scene `items` (a list as for synth_tx_list(), or a numpy array of
+    SYNTH_TX_DTYPE; amp and noise_sigma in PCM units) into nseg records of nsamp int16 samples at the raw device pointer
+    d_pcm (row stride pcm_stride samples), the rows audio_batch_device() takes.  n_clipped: an int32 numpy array of nseg that
+    receives the clipped samples per record, or None.  Returns the library's code (0; -1 with nothing written; -2 for
+    nsamp > AUDIO_MAX_SAMPLES)."""
+    tx, n, _keep = _synth_items(items)
+    return lib().wspr_synth_audio_batch_device(tx, n, int(nseg), int(seg_index0), int(nsamp), noise_sigma, seed, int(flags),
+                                               d_pcm, int(pcm_stride), None if n_clipped is None else _ptr(n_clipped))
+
+
+def synth_audio(items, nsamp=AUDIO_MAX_SAMPLES, noise_sigma=0.0, seed=0, flags=0, pcm=None):
+    """wspr_synth_audio(): one record of nsamp int16 samples in host memory (a given record is copied and matters with
+    SYNTH_ACCUMULATE).  Returns (pcm, n_clipped); raises if the library refuses the call."""
+    pcm = np.zeros(int(nsamp), np.int16) if pcm is None else np.array(pcm, np.int16).copy()
+    assert pcm.size == int(nsamp)
+    tx, n, _keep = _synth_items(items)
+    clipped = C.c_int(0)
+    rc = lib().wspr_synth_audio(tx, n, int(nsamp), noise_sigma, seed, int(flags), _ptr(pcm), C.addressof(clipped))
+    if rc != 0:
+        raise RuntimeError("wspr_synth_audio failed (rc %d: bad arguments, a record above 120 s, or no usable HIP device)" % rc)
+    return pcm, int(clipped.value)
 
 
 def audio_constants():

@@ -88,6 +88,7 @@ int wspr_read_c2_file(const char* filename, float* I, float* Q, double* dial_hz)
 
 // One slot of 12 000 Hz 16-bit mono audio (the parser, plain C++: wspr_wav.cpp)
 size_t wspr_read_wav_file(const char* filename, int16_t* pcm, size_t cap) { return wspr::read_wav_file(filename, pcm, cap); }
+int wspr_write_wav_file(const char* filename, const int16_t* pcm, size_t nsamp) { return wspr::write_wav_file(filename, pcm, nsamp); }
 
 // writeRawIQfile(), rtlsdr_wsprd.c:595-617: always 45000 complex samples, Q negated.
 int wspr_write_iq_file(const char* filename, const float* I, const float* Q) {

@@ -253,6 +253,11 @@ public:
     int synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, float sigma, uint64_t seed,
                      int flags, float* dI, float* dQ, const FadeChannel* fade = nullptr);
     float* synth_rows();            // two rows of kIqStride floats of the context's own (wspr_selftest)
+    // K17 (wspr_capi_audio_synth.hip; the definition in kernels/audio_synth.h): a validated, sorted transmission list into
+    // nseg validated device records of nsamp 16-bit samples; h_clipped (nseg, may be null) = samples clipped of each;
+    // complete on return
+    int synth_audio_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, int nsamp, float sigma,
+                           uint64_t seed, int flags, int16_t* d_pcm, size_t pcm_stride, int* h_clipped);
 
     struct Impl;
     struct DecodeRun;               // state of one decode_core() call (wspr_pipeline.hip)

@@ -66,4 +66,35 @@ size_t read_wav_file(const char* filename, int16_t* pcm, size_t cap) {
     fclose(fd);
     return n;
 }
+
+// The canonical 44-byte header (RIFF, "fmt " of 16 bytes, data) and the samples, little-endian whatever the host is.
+int write_wav_file(const char* filename, const int16_t* pcm, size_t nsamp) {
+    if (!filename || (!pcm && nsamp) || nsamp > (0xffffffffu - 36u) / 2u) return -1;   // the size fields are 32 bits
+    FILE* fd = fopen(filename, "wb");
+    if (!fd) { fprintf(stderr, "Cannot open data file...\n"); return -1; }
+    const uint32_t data = (uint32_t)(nsamp * 2), rate = 12000;
+    unsigned char hd[44];
+    auto put32 = [&](int at, uint32_t v) { for (int b = 0; b < 4; ++b) hd[at + b] = (unsigned char)(v >> (8 * b)); };
+    auto put16 = [&](int at, uint32_t v) { hd[at] = (unsigned char)v; hd[at + 1] = (unsigned char)(v >> 8); };
+    memcpy(hd, "RIFF", 4);      put32(4, 36u + data);
+    memcpy(hd + 8, "WAVEfmt ", 8);  put32(16, 16);
+    put16(20, 1);               put16(22, 1);               // PCM, one channel
+    put32(24, rate);            put32(28, rate * 2);        // samples and bytes per second
+    put16(32, 2);               put16(34, 16);              // bytes per frame, bits per sample
+    memcpy(hd + 36, "data", 4); put32(40, data);
+    bool ok = fwrite(hd, 1, sizeof hd, fd) == sizeof hd;
+    unsigned char buf[4096];
+    for (size_t done = 0; ok && done < nsamp;) {
+        const size_t n = nsamp - done < sizeof buf / 2 ? nsamp - done : sizeof buf / 2;
+        for (size_t i = 0; i < n; ++i) {
+            const uint16_t v = (uint16_t)pcm[done + i];
+            buf[2 * i] = (unsigned char)v;
+            buf[2 * i + 1] = (unsigned char)(v >> 8);
+        }
+        ok = fwrite(buf, 2, n, fd) == n;
+        done += n;
+    }
+    if (fclose(fd) != 0) ok = false;
+    return ok ? 0 : -1;
+}
 }  // namespace wspr

@@ -276,6 +276,16 @@ void audio_front_taps(float* gi511, float* gq511);                  // the two t
 // guard = 0 .. 64.  n_blanked: one device counter per record, ADDED to (the caller zeroes it).
 void launch_audio_blank(const int16_t* pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, int16_t* out,
                         size_t out_stride, int* n_blanked, hipStream_t st);
+// K17, the 12 kHz audio scene synthesiser (k17_audio_synth.hip; the definition in audio_synth.h).  tx, seg_off, first as for
+// launch_synth(); phase: audio_synth_phase_doubles(ntx) doubles of scratch.  nseg records of nsamp samples (rows as K15's
+// output rows: pcm 16-byte aligned, pcm_stride a multiple of 8 and >= nsamp, 0 <= nsamp <= 1 440 000): columns
+// 0 .. roundup8(nsamp) - 1 written (from nsamp on zero, or with `accumulate` what they held), the rest left alone.
+// n_clipped: one device counter per record, ADDED to (the caller zeroes it).
+constexpr int kAudioSynthTile = 2048;                     // samples of a record per workgroup
+size_t audio_synth_phase_doubles(int ntx);
+void launch_audio_synth(const SynthTx* tx, int ntx, const int* seg_off, int nseg, long long seg_index0, int nsamp, float sigma,
+                        unsigned long long seed, int accumulate, double* phase, int* first, int16_t* pcm, size_t pcm_stride,
+                        int* n_clipped, hipStream_t st);
 // K16, the band noise figures of a segment (k16_noise.hip; the definition in noise.h): nseg rows of `samples` samples
 // (0 .. kMaxSamples; rows 16-byte aligned, stride a multiple of 4 floats and >= samples; nothing at or behind `samples` is
 // read) into nseg records of 32 bytes (noise::Result) at out.  table: noise::kTableFloats floats of noise::noise_tables(),
