@@ -113,6 +113,13 @@ int wspr_bench_fft_sync(const void *d_idat, const void *d_qdat, int nseg, int sa
 int wspr_bench_valu(const void *d_idat, const void *d_qdat, int nseg, int samples, size_t seg_stride,
                     int iters, double *ms);
 
+/* Vectors for which the device Fano search (K6w) returned -2 (its pending-visit store overflowed) and which the serial
+ * host decoder finished instead, counted since the process began: *on_pool = those of calls that had the vectors on the
+ * host (wspr_fano_batch_device_wave), *one_by_one = those fetched from the device one at a time (the decode loop with
+ * wspr_set_fano_device_mode(1)).  Either pointer may be NULL.  With the production store of 4 096 visits both stay 0 in
+ * every test; WSPR_FANO_WAVE_CAP=96 (a store of 96 visits; 1024 is the other value it accepts) makes them move. */
+void wspr_fano_host_handovers(unsigned long long *on_pool, unsigned long long *one_by_one);
+
 /* CUs the whole-segment front end (K0) may occupy: 0 = all (default; env WSPR_K0_CUS), else its kernels run on a
  * stream restricted to that many CUs (hipExtStreamCreateWithCUMask, spread over the XCDs), so that a decoder running
  * on another lane keeps the rest of the chip: K0 is HBM-bound and needs bandwidth, not every CU.  Returns the

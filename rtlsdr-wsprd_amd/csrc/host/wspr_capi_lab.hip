@@ -248,6 +248,11 @@ int wspr_set_front_end_cus(int ncus) {
     return wspr::front_end_cus().exchange(ncus < 0 ? 0 : ncus);
 }
 
+void wspr_fano_host_handovers(unsigned long long* on_pool, unsigned long long* one_by_one) {
+    if (on_pool) *on_pool = wspr::fano_handovers(0).load();
+    if (one_by_one) *one_by_one = wspr::fano_handovers(1).load();
+}
+
 int wspr_bench_decimate(const void* d_raw, size_t bytes_per_seg, int nseg, void* d_idat, void* d_qdat, int iters,
                         double* ms) {
     LaneTurn lane_turn;

@@ -28,6 +28,11 @@ std::atomic<int>& pool_workers_alive();
 std::atomic<int>& node_share();
 // CUs the front end (K0) may occupy, 0 = all (wspr_set_front_end_cus / WSPR_K0_CUS)
 std::atomic<int>& front_end_cus();
+#ifdef WSPR_LAB
+// vectors K6w returned as -2 and Context::fano_resident() handed to the serial host decoder since the process began:
+// [0] on the pool (the caller had a host copy), [1] one by one after a fetch (wspr_fano_host_handovers)
+std::atomic<unsigned long long>& fano_handovers(int branch);
+#endif
 
 // The five process-wide settings a decode call honours: wspr_set_arithmetic() (0 exact, 1 contracted),
 // wspr_set_osd_depth() (-1 off, 0..3), wspr_set_block_detection() (1 off, 2, 3), wspr_set_spread_estimate() (0 off, 1 on)

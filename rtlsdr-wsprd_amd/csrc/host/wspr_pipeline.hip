@@ -1440,9 +1440,18 @@ static const unsigned char* stage_vectors(Context::Impl& c, const unsigned char*
     return dsym;
 }
 
+#ifdef WSPR_LAB
+std::atomic<unsigned long long>& fano_handovers(int branch) {
+    static std::atomic<unsigned long long> count[2];
+    return count[branch != 0];
+}
+#endif
+
 // The wave-parallel search (K6w).  metric / maxnp (both or neither) and steps are optional outputs.  The kernel reports -2
-// for a vector whose pending-visit store overflowed (not seen in tests); the serial host decoder takes those: over
-// h_symbols (the vectors' host copy, vector i at i * 162) on the pool, else one by one after fetching the vector.
+// for a vector whose pending-visit store overflowed (never with the production store of 4 096 visits in any test vector:
+// tests/test_gpu_fano_wave.py asserts that the counter below stays 0 there, and runs both branches with the lab store of
+// 96 visits, WSPR_FANO_WAVE_CAP=96); the serial host decoder takes those: over h_symbols (the vectors' host copy,
+// vector i at i * 162) on the pool, else one by one after fetching the vector.
 int Context::fano_resident(const unsigned char* d_symbols, const int* h_offsets, int n, unsigned maxcycles, int* ret,
                            unsigned* cycles, unsigned char* data, unsigned* metric, unsigned* maxnp, unsigned* steps,
                            const unsigned char* h_symbols) {
@@ -1471,6 +1480,9 @@ int Context::fano_resident(const unsigned char* d_symbols, const int* h_offsets,
     std::vector<int> redo;
     for (int i = 0; i < n; ++i) if (ret[i] == -2) redo.push_back(i);
     if (redo.empty()) return 0;
+#ifdef WSPR_LAB
+    fano_handovers(h_symbols ? 0 : 1) += redo.size();
+#endif
     const FanoMetrics& met = default_metrics();
     auto serial = [&](int k) {
         const int i = redo[k];

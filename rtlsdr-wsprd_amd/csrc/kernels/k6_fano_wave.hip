@@ -61,7 +61,11 @@ void fano_wave_kernel(const unsigned char* __restrict__ symbols, const int* __re
                       unsigned* __restrict__ maxnp, unsigned char* __restrict__ data, unsigned* __restrict__ steps_out,
                       uint32_t* __restrict__ gpool, int* __restrict__ next_vector) {
     // entry i of the stack is in LDS slot i & (kWin - 1) while lo <= i < lo + kWin (lo: wave-uniform, a multiple of
-    // kHalf); entries below lo are in the wave's slice of device memory gp[arr][i]
+    // kHalf); entries below lo are in the wave's slice of device memory gp[arr][i].  size <= kCap throughout (a step takes at
+    // most room / 2 visits and a visit adds at most 2 net; after a cut, at most 3 * take - 2 <= kCap - 2 remain), so a store
+    // no larger than the window (the lab's 96) keeps lo = 0: it never spills or fills, and never touches gp
+    static_assert(kCap >= 4 && kCap <= 4096 && (kCap <= kWin || kCap % kHalf == 0),
+                  "a store is one window at most, or whole half-windows within the 5 * 4096-word slice");
     __shared__ uint32_t lpool[5 * kWin];
     uint32_t* __restrict__ gp = gpool + (size_t)blockIdx.x * 5 * kCap;
     auto ld = [&](int arr, int i) -> uint32_t { return lpool[arr * kWin + (i & (kWin - 1))]; };
@@ -274,10 +278,15 @@ void launch_fano_wave(const unsigned char* symbols, const int* offsets, int n, c
     (void)hipMemsetAsync(counter, 0, sizeof(int), st);
     // WSPR_FANO_WAVE_CAP=1024 (test hook, tests/test_gpu_parity.py): a stack of 1 024 visits instead of 4 096, so that the
     // narrowed steps (8 visits, then 1, as the stack fills), the window's spills and fills at those widths and the
-    // overflow exit (-2: the caller's host routine takes the vector) are exercised by ordinary time-out vectors
-    static const bool small = [] { const char* e = lab_env("WSPR_FANO_WAVE_CAP"); return e && atoi(e) == 1024; }();
-    if (small)
+    // 1-wide step are exercised by ordinary time-out vectors (tests/test_fano_cases_cpu.py counts them).  =96: a stack of
+    // 96 visits, which many ordinary vectors overflow (-2: the caller's host routine takes the vector); the window never
+    // moves at that size (see the kernel's static assertion); the scratch stays 5 * 4096 words per wave whatever the store
+    static const int small = [] { const char* e = lab_env("WSPR_FANO_WAVE_CAP"); return e ? atoi(e) : 0; }();
+    if (small == 1024)
         hipLaunchKernelGGL((fano_wave_kernel<1024>), dim3(grid), dim3(64), 0, st, symbols, offsets, n, metric0, maxcycles,
+                           ret, cycles, metric, maxnp, data, steps, scratch, counter);
+    else if (small == 96)
+        hipLaunchKernelGGL((fano_wave_kernel<96>), dim3(grid), dim3(64), 0, st, symbols, offsets, n, metric0, maxcycles,
                            ret, cycles, metric, maxnp, data, steps, scratch, counter);
     else
         hipLaunchKernelGGL((fano_wave_kernel<4096>), dim3(grid), dim3(64), 0, st, symbols, offsets, n, metric0, maxcycles,

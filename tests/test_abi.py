@@ -48,7 +48,7 @@ def test_lab_library_is_the_product_plus_the_bench_header():
     assert {"wspr_decode_batch_trace", "wspr_stage_fft_bank", "wspr_stage_candidates", "wspr_stage_candidates_ps", "wspr_bench_fft_sync",
             "wspr_bench_valu",
             "wspr_bench_decimate", "wspr_calib_read", "wspr_calib_copy", "wspr_calib_copy16", "wspr_calib_valu",
-            "wspr_set_front_end_cus"} == bfuncs and not bdata
+            "wspr_set_front_end_cus", "wspr_fano_host_handovers"} == bfuncs and not bdata
     out = subprocess.run(["nm", "-D", "--defined-only", w.LAB_PATH], capture_output=True, text=True, check=True).stdout
     exported = {ln.split()[-1] for ln in out.splitlines() if ln.strip()}
     assert exported == funcs | data | bfuncs

@@ -79,6 +79,20 @@ def test_wave_search_equals_serial_decoder_and_golden(fw, golden_vectors):
     assert worst_store <= 1024
 
 
+def test_small_store_overflow_is_the_only_difference():
+    """The small store (64, 160) of the test above has simply not met a vector that overflows it: of its 600 vectors none
+    does.  Of the 364 ladder vectors of tests/fano_lib.py two do at the full budget (and none at 50): there -2, the
+    hand-over to the serial decoder, is the only way the search may differ from it."""
+    import fano_lib as fl
+    for budget, n_over in ((50, 0), (10000, 2)):
+        wav = fl.wave_of("ladder", budget, 64, 160)
+        ser = fl.serial_of("ladder", budget, "product")
+        over = wav[:, 0] == -2
+        assert int(over.sum()) == n_over
+        assert (fl.defined(wav[~over]) == ser[~over]).all()
+        assert (wav[over][:, 1:14] == 0).all() and (ser[over][:, 0] == -1).all()
+
+
 def test_wave_search_degenerate_vectors(fw):
     """All-erasure, saturated and alternating soft symbols: thin and bushy trees, thresholds far below 0."""
     L = w.lib()

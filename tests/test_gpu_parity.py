@@ -866,7 +866,9 @@ def test_wave_fano_equals_host_fano(w):
 def test_wave_fano_with_a_small_stack_in_a_subprocess():
     """K6w with a stack of 1 024 visits (test hook WSPR_FANO_WAVE_CAP, read once per process): the same vectors and the
     same assertions as test_wave_fano_equals_host_fano, now through the narrowed steps and the LDS window's spills and
-    fills at those widths; a vector whose stack overflows all the same is finished by the host routine (exact)."""
+    fills at those widths.  None of these vectors overflows that stack (the largest holds 777 visits; only one reaches the
+    1-wide step, at the full budget): the overflow exit and the host routine behind it are not met here but in
+    tests/test_gpu_fano_wave.py, with a stack of 96."""
     import subprocess
     import sys
     env = dict(os.environ, WSPR_FANO_WAVE_CAP="1024", WSPR_USE_LAB="1")      # the switch exists in the lab build only
