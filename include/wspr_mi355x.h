@@ -505,6 +505,48 @@ int wspr_synth_audio_batch_device(const wspr_synth_tx *tx, int ntx, int nseg, in
 int wspr_synth_audio(const wspr_synth_tx *tx, int ntx, int nsamp, float noise_sigma, uint64_t seed, int flags,
                      int16_t *pcm, int *n_clipped);
 
+/* ---- IQ to audio (K18) ------------------------------------------------------------------------------------------
+ * The way back from the decoder's rows to audio: a slot that exists only as 375 Hz IQ -- a receiver capture behind
+ * wspr_decimate_u8*(), a .iq or .c2 file, a scene of wspr_synth*(), the residual a decode call writes back -- becomes the
+ * 12 000 Hz, 16-bit, mono record with the band at 1 500 Hz that wspr_audio_batch_device(), wspr_write_wav_file(), WSJT-X's
+ * wsprd and wsprdaemon archives take.  It is the transpose of the audio front end over that stage's own two tap tables
+ * (wspr_audio_constants(): gI[k], gQ[k], k = -255 .. 255); no table of its own.  A CPU reproduces every sample bit for bit
+ * (rtlsdr-wsprd_amd/csrc/kernels/iq_audio.h is the definition, tests/helpers/iq_audio_check.c its serial form).
+ * wspr_set_arithmetic() does not touch this stage.
+ *
+ * For one row of np samples (0 .. 45 000) of I and Q the record has 32 np samples.  Output sample n, in this order:
+ *   acc = +0.0f
+ *   for every m with 0 <= m < np and |n - 32 m| <= 255, IN RISING m, with k = n - 32 m:
+ *       acc = fmaf(gI[k], I[m], acc)        unless k = 2, 6 (mod 8)
+ *       acc = fmaf(gQ[k], Q[m], acc)        unless k = 0, 4 (mod 8)        (k mod 8 non-negative)
+ *   y = 16.0f * acc
+ *   p = (double)y * (double)gain
+ *   p is NaN: the sample is 0 and counts as clipped.  Otherwise step 4 of the audio scene synthesiser above: p > 32767.0
+ *   gives 32767, p < -32768.0 gives -32768, either counts as clipped, else (p + 6755399441055744.0) - 6755399441055744.0
+ *   (nearest, ties to even) as an int16.  n_clipped[s] is the record's count.
+ * Nothing else is fused or reordered.  The taps named in the two "unless" are +0.0f, but the input is float and may be Inf
+ * or NaN, so leaving those steps out IS the definition, not a shortcut: output n takes I alone for n = 0, 4 (mod 8), Q alone
+ * for n = 2, 6 (mod 8), both for odd n; at most 16 inputs and 24 multiply-adds per output.
+ * SCALE AND TIME: a phasor A e^{+j 2 pi f m / 375} leaves as A cos(2 pi (1500 + f) n / 12000) -- a tone at +f in the decoder's
+ * convention is audio at 1500 + f Hz.  gain = 32768 is the inverse of the front end's 2^-15 and suits rows normalised to a
+ * peak of 0.5.  Output n = 32 m is centred on input m: no delay is added in either direction, and this call followed by
+ * wspr_audio_batch_device() is the identity inside the search band up to that filter's ripple, twice (1.4e-4 relative at
+ * +-110 Hz), and the 16-bit rounding.
+ *
+ * wspr_iq_to_audio_batch_device(): input rows as for wspr_noise_batch_device() (d_idat, d_qdat 16-byte aligned device
+ * memory, seg_stride floats apart, a multiple of 4 and >= samples; nothing at or behind `samples` is read); output rows as
+ * for wspr_synth_audio_batch_device() (d_pcm 16-byte aligned device memory, pcm_stride a multiple of 8 and >= 32 * samples).
+ * Columns 0 .. 32 * samples - 1 are written; the columns behind them and the input are left alone.  Returns 0; -1 with a
+ * line on stderr and NOTHING WRITTEN (n_clipped included) for: no device, negative counts, misalignment, a stride that is
+ * too small or no multiple of its unit, a non-finite gain; -2 for samples > 45 000.  nseg == 0 does nothing, samples == 0
+ * writes no sample (n_clipped: zeros).  Stream contract and lane turn as wspr_audio_batch_device(); the scratch (one counter
+ * per record) belongs to the lane's context and is returned by wspr_release_buffers(). */
+int wspr_iq_to_audio_batch_device(const void *d_idat, const void *d_qdat, int nseg, int samples, size_t seg_stride,
+                                  float gain, void *d_pcm, size_t pcm_stride, int *n_clipped /* host, nseg, may be NULL */);
+/* One row of host memory into a record of 32 * samples int16 in host memory: row 0 of the batch call.  n_clipped: one
+ * int, may be NULL. */
+int wspr_iq_to_audio(const float *I, const float *Q, int samples, float gain, int16_t *pcm /* 32*samples */, int *n_clipped);
+
 /* ---- receiver session --------------------------------------------------------------------
  * The reference's rx_state (two I/Q buffers of 45000 samples, their fill counters, the active index,
  * rtlsdr_wsprd.c:78-90), the decimator's static state (:135-160) and the body of its decoder thread (:263-328) as
@@ -561,6 +603,10 @@ size_t wspr_read_wav_file(const char *filename, int16_t *pcm, size_t cap);
 int wspr_write_wav_file(const char *filename, const int16_t *pcm, size_t nsamp);
 /* Replaces writeRawIQfile(), reference rtlsdr_wsprd.c:595-617. */
 int wspr_write_iq_file(const char *filename, const float *I, const float *Q);
+/* Exactly what wspr_read_c2_file() reads: 14 name bytes (the file's base name, cut or padded with zeros), int type 2,
+ * double dial frequency in Hz, then 45000 interleaved pairs (I, -Q) of float32.  I/Q: 45000 floats each.  Returns the
+ * samples written (45000), 0 on error, like wspr_write_iq_file().  Host code: needs no device. */
+int wspr_write_c2_file(const char *filename, const float *I, const float *Q, double dial_hz);
 /* The "Spot : ..." line of decodeRecordedFile(), reference rtlsdr_wsprd.c:691-701. */
 int wspr_format_spot(const struct decoder_results *r, char *out, size_t cap);
 

@@ -196,6 +196,13 @@ def _bind(path):
     L.wspr_synth_audio_batch_device.restype = C.c_int
     L.wspr_synth_audio.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p]
     L.wspr_synth_audio.restype = C.c_int
+    L.wspr_iq_to_audio_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_float, C.c_void_p,
+                                                C.c_size_t, C.c_void_p]
+    L.wspr_iq_to_audio_batch_device.restype = C.c_int
+    L.wspr_iq_to_audio.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_void_p]
+    L.wspr_iq_to_audio.restype = C.c_int
+    L.wspr_write_c2_file.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_double]
+    L.wspr_write_c2_file.restype = C.c_int
     L.wspr_selftest.argtypes = [decoder_options, C.c_void_p]
     L.wspr_selftest.restype = C.c_int
     L.nhash.restype = C.c_uint32
@@ -656,6 +663,48 @@ def synth_audio(items, nsamp=AUDIO_MAX_SAMPLES, noise_sigma=0.0, seed=0, flags=0
     if rc != 0:
         raise RuntimeError("wspr_synth_audio failed (rc %d: bad arguments, a record above 120 s, or no usable HIP device)" % rc)
     return pcm, int(clipped.value)
+
+
+IQ_AUDIO_INTERP = 32               # include/wspr_mi355x.h: IQ to audio (K18), output samples per input sample
+IQ_AUDIO_GAIN = 32768.0            # the inverse of the audio front end's 2^-15: for rows normalised to a peak of 0.5
+
+
+def iq_to_audio_batch_device(d_i, d_q, nseg, samples, seg_stride, d_pcm, pcm_stride, gain=IQ_AUDIO_GAIN, n_clipped=None):
+    """wspr_iq_to_audio_batch_device(): nseg rows of `samples` floats at the raw device pointers d_i / d_q (16-byte aligned,
+    seg_stride floats apart) into nseg records of 32 * samples int16 samples at the raw device pointer d_pcm (row stride
+    pcm_stride samples), the rows audio_batch_device() takes.  n_clipped: an int32 numpy array of nseg that receives the
+    clipped samples per record, or None.  Returns the library's code (0; -1 with nothing written; -2 for samples > 45000)."""
+    return lib().wspr_iq_to_audio_batch_device(d_i, d_q, int(nseg), int(samples), int(seg_stride), gain, d_pcm,
+                                               int(pcm_stride), None if n_clipped is None else _ptr(n_clipped))
+
+
+def iq_to_audio(I, Q, gain=IQ_AUDIO_GAIN, samples=None):
+    """wspr_iq_to_audio(): one host row (float32, 375 Hz) into a record of 32 * samples int16 samples at 12 000 Hz with the
+    band at 1 500 Hz, through the device.  Returns (pcm, n_clipped); raises if the library refuses the call."""
+    I = np.ascontiguousarray(I, dtype=np.float32)
+    Q = np.ascontiguousarray(Q, dtype=np.float32)
+    n = int(min(I.size, Q.size) if samples is None else samples)
+    assert 0 <= n <= min(I.size, Q.size)
+    pcm = np.zeros(IQ_AUDIO_INTERP * n, np.int16)
+    clipped = C.c_int(0)
+    rc = lib().wspr_iq_to_audio(_ptr(I), _ptr(Q), n, gain, _ptr(pcm), C.addressof(clipped))
+    if rc != 0:
+        raise RuntimeError("wspr_iq_to_audio failed (rc %d: a non-finite gain, more than 45000 samples, or no usable HIP "
+                           "device)" % rc)
+    return pcm, int(clipped.value)
+
+
+def write_c2_file(filename, I, Q, dial_hz):
+    """wspr_write_c2_file(): 45000 samples of I and Q (shorter rows are padded with zeros) and the dial frequency in Hz as a
+    .c2 file, what wspr_read_c2_file() reads.  Raises if the file cannot be written.  Host code: needs no device."""
+    rows = []
+    for x in (I, Q):
+        x = np.ascontiguousarray(x, dtype=np.float32).ravel()
+        if x.size > NSAMPLES:
+            raise ValueError("a .c2 file holds 45000 samples")
+        rows.append(np.concatenate((x, np.zeros(NSAMPLES - x.size, np.float32))))
+    if lib().wspr_write_c2_file(os.fsencode(filename), _ptr(rows[0]), _ptr(rows[1]), float(dial_hz)) != NSAMPLES:
+        raise OSError("wspr_write_c2_file could not write %r" % (filename,))
 
 
 def audio_constants():

@@ -1,8 +1,10 @@
 // C ABI of libwspr_mi355x.so (declared in include/wspr_mi355x.h): recorded-file formats, the frame time
 // and the spot / report texts.  Host code only.
+#include <algorithm>
 #include <cctype>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <ctime>
 #include <string>
 #include <vector>
@@ -99,6 +101,28 @@ int wspr_write_iq_file(const char* filename, const float* I, const float* Q) {
     const size_t nw = fwrite(buf.data(), sizeof(float), buf.size(), fd);
     fclose(fd);
     if (nw != buf.size()) { fprintf(stderr, "Cannot write all the data!\n"); return 0; }
+    return wspr::kMaxSamples;
+}
+
+// What wspr_read_c2_file() reads (readC2file(), rtlsdr_wsprd.c:620-667; the reference has no writer for it): the file's base
+// name in 14 bytes (cut or padded with zeros), int type 2, the dial frequency as a double, then writeRawIQfile()'s payload.
+int wspr_write_c2_file(const char* filename, const float* I, const float* Q, double dial_hz) {
+    if (!filename || !I || !Q) { fprintf(stderr, "Cannot open data file...\n"); return 0; }
+    FILE* fd = fopen(filename, "wb");
+    if (!fd) { fprintf(stderr, "Cannot open data file...\n"); return 0; }
+    const char* base = strrchr(filename, '/');
+    base = base ? base + 1 : filename;
+    char name[14] = {0};
+    memcpy(name, base, std::min<size_t>(strlen(base), sizeof name));
+    const int type = 2;
+    std::vector<float> buf(2 * (size_t)wspr::kMaxSamples);
+    for (int i = 0; i < wspr::kMaxSamples; ++i) { buf[2 * i] = I[i]; buf[2 * i + 1] = -Q[i]; }
+    size_t nw = fwrite(name, sizeof(char), sizeof name, fd);
+    nw += fwrite(&type, sizeof(int), 1, fd);
+    nw += fwrite(&dial_hz, sizeof(double), 1, fd);
+    nw += fwrite(buf.data(), sizeof(float), buf.size(), fd);
+    const bool closed = fclose(fd) == 0;
+    if (nw != sizeof name + 2 + buf.size() || !closed) { fprintf(stderr, "Cannot write all the data!\n"); return 0; }
     return wspr::kMaxSamples;
 }
 

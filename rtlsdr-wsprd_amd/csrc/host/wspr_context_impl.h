@@ -250,7 +250,8 @@ struct Context::Impl {
         synthfade,   // K13: one FadeChannel per transmission
         blankrows, blankcount,   // K15: at most Context::kBlankChunk blanked records on their way to K12; one counter per record
         noise_tab, noise_out,    // K16: twiddles and window (built on first use); one 32-byte record per segment
-        asynthphase, asynthcount;   // K17: P_i and dphi_i of each transmission (list, offsets and first indices are K8's buffers); one counter per record
+        asynthphase, asynthcount,   // K17: P_i and dphi_i of each transmission (list, offsets and first indices are K8's buffers); one counter per record
+        iqaudiocount;   // K18: one counter per record
     double noise_w2 = 0.0;       // K16: the sum of the squared window, from the same pass as the table
     PinBuf h_npk, h_cand, h_items, h_sync, h_sym, h_rms, h_jobs, h_jobs2, h_seglist, h_misc, h_lists;
     // host-buffer entry (wspr_decode_batch: the reference's calling convention, wsprd.h:106-111): pageable caller rows

@@ -263,6 +263,11 @@ public:
     // complete on return
     int synth_audio_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, int nsamp, float sigma,
                            uint64_t seed, int flags, int16_t* d_pcm, size_t pcm_stride, int* h_clipped);
+    // K18 (wspr_capi_iq_audio.hip; the definition in kernels/iq_audio.h): nseg validated device rows of `samples` samples into
+    // nseg validated device records of 32 * samples 16-bit samples; h_clipped (nseg, may be null) = samples clipped of each;
+    // complete on return
+    int iq_audio_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, float gain, int16_t* d_pcm,
+                        size_t pcm_stride, int* h_clipped);
 
     struct Impl;
     struct DecodeRun;               // state of one decode_core() call (wspr_pipeline.hip)

@@ -286,6 +286,13 @@ size_t audio_synth_phase_doubles(int ntx);
 void launch_audio_synth(const SynthTx* tx, int ntx, const int* seg_off, int nseg, long long seg_index0, int nsamp, float sigma,
                         unsigned long long seed, int accumulate, double* phase, int* first, int16_t* pcm, size_t pcm_stride,
                         int* n_clipped, hipStream_t st);
+// K18, IQ to audio (k18_iq_audio.hip; the definition in iq_audio.h): nseg rows of `samples` samples (0 .. kMaxSamples; rows as
+// for K16: 16-byte aligned, stride a multiple of 4 floats and >= samples, nothing at or behind `samples` is read) into nseg
+// records of 32 * samples 16-bit samples (rows as K17's: pcm 16-byte aligned, pcm_stride a multiple of 8 and >= 32 * samples):
+// columns 0 .. 32 * samples - 1 written, the rest left alone.  gain: finite.  n_clipped: one device counter per record,
+// ADDED to (the caller zeroes it).
+void launch_iq_audio(const float* dI, const float* dQ, size_t stride, int samples, int nseg, float gain, int16_t* pcm,
+                     size_t pcm_stride, int* n_clipped, hipStream_t st);
 // K16, the band noise figures of a segment (k16_noise.hip; the definition in noise.h): nseg rows of `samples` samples
 // (0 .. kMaxSamples; rows 16-byte aligned, stride a multiple of 4 floats and >= samples; nothing at or behind `samples` is
 // read) into nseg records of 32 bytes (noise::Result) at out.  table: noise::kTableFloats floats of noise::noise_tables(),
