@@ -428,12 +428,7 @@ def wspr_synth_batch_device(items, nseg, d_i, d_q, seg_index0=0, noise_sigma=0.0
     """wspr_synth_batch_device() of include/wspr_mi355x.h: the scene `items` (a list as for synth_tx_list(), or a numpy
     array of SYNTH_TX_DTYPE) into nseg device rows of wspr_iq_stride() floats at the raw pointers d_i / d_q.
     Returns the library's code (0, or -1 with nothing written)."""
-    if isinstance(items, np.ndarray):
-        assert items.dtype == SYNTH_TX_DTYPE and items.flags.c_contiguous
-        tx, n = items.ctypes.data, int(items.size)
-    else:
-        arr = synth_tx_list(items)
-        tx, n = C.addressof(arr), len(items)
+    tx, n, _keep = _synth_items(items)
     return lib().wspr_synth_batch_device(tx, n, nseg, seg_index0, noise_sigma, seed, flags, d_i, d_q)
 
 
@@ -476,12 +471,7 @@ def wspr_synth_faded_batch_device(items, channels, nseg, d_i, d_q, seg_index0=0,
     """wspr_synth_faded_batch_device(): wspr_synth_batch_device() with an HF fading channel per transmission (K13).
     channels: one [(gain, shift, sigma), (gain, shift, sigma)] per transmission (or a numpy array of SYNTH_CHANNEL_DTYPE);
     None is the unfaded call.  Returns the library's code (0, or -1 with nothing written)."""
-    if isinstance(items, np.ndarray):
-        assert items.dtype == SYNTH_TX_DTYPE and items.flags.c_contiguous
-        tx, n = items.ctypes.data, int(items.size)
-    else:
-        arr = synth_tx_list(items)
-        tx, n = C.addressof(arr), len(items)
+    tx, n, _keep_tx = _synth_items(items)
     ch, _keep = _synth_channels(channels, n)
     return lib().wspr_synth_faded_batch_device(tx, ch, n, nseg, seg_index0, noise_sigma, seed, flags, d_i, d_q)
 

@@ -12,11 +12,11 @@
 #include <vector>
 
 #include "wspr_capi_impl.h"
-#include "../kernels/audio_blank.h"
-#include "../kernels/audio_front.h"
+#include "wspr_stage_args.h"
 
 using wspr::Context;
 using namespace wspr::capi;
+namespace args = wspr::args;
 
 // ---- receiver session: the reference's double buffer and decoder thread body ----------------
 // rx_state of rtlsdr_wsprd.c:78-90 (two I/Q buffers, their fill counters, the active index) plus the
@@ -117,68 +117,22 @@ int wspr_decimate_u8(const uint8_t* iq, size_t nbytes, float* I, float* Q, uint3
         int nout = 0;
         const int rc = c.decimate_device(raw.p, nbytes, 1, wi, wq, normalise, &nout);
         if (rc) return rc;
-        HIP_TRY(hipMemcpy(I, wi, (size_t)wspr::kMaxSamples * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(Q, wq, (size_t)wspr::kMaxSamples * 4, hipMemcpyDeviceToHost));
+        rows_down(I, Q, wi, wq);
         if (n_out) *n_out = (uint32_t)nout;
         return 0;
     } catch (const std::exception& e) { return fail("wspr_decimate_u8", e); }
 }
 
-// ---- K12, the 12 kHz audio front end (kernels/audio_front.h) ----------------------------------------------------------
-// (the texts name no macro: tests/test_abi.py limits the macro-style names the product binary carries)
-static int audio_args_bad(const char* where, const void* d_pcm, size_t pcm_stride, long long nsamp, int nseg, const void* d_i,
-                          const void* d_q) {
-    const char* why = nullptr;
-    if (nseg < 0 || nsamp < 0) why = "negative count";
-    else if (nsamp > AUDIO_FRONT_MAX_SAMPLES) {
-        fprintf(stderr, "libwspr_mi355x: %s: a record holds at most 1440000 samples (120 s); longer ones are refused, not cut\n", where);
-        return -2;
-    }
-    else if (nseg > 0 && (!d_pcm || (reinterpret_cast<uintptr_t>(d_pcm) & 15))) why = "d_pcm must be 16-byte aligned device memory";
-    else if (nseg > 0 && ((pcm_stride & 7) || pcm_stride < (size_t)nsamp)) why = "pcm_stride must be a multiple of 8 and at least nsamp";
-    else if (nseg > 0 && (!d_i || !d_q || ((reinterpret_cast<uintptr_t>(d_i) | reinterpret_cast<uintptr_t>(d_q)) & 15)))
-        why = "d_idat and d_qdat must be 16-byte aligned device rows";
-    if (why) { fprintf(stderr, "libwspr_mi355x: %s: %s\n", where, why); return -1; }
-    return 0;
-}
-
+// ---- K12, the 12 kHz audio front end (kernels/audio_front.h), and K15, the impulse-noise blanker in front of it
+// (kernels/audio_blank.h) ---------------------------------------------------------------------------------------------
 int wspr_audio_batch_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, void* d_idat, void* d_qdat,
                             int normalise) {
+    static const char* where = "wspr_audio_batch_device";
     LaneTurn lane_turn;
     try {
-        if (const int bad = audio_args_bad("wspr_audio_batch_device", d_pcm, pcm_stride, nsamp, nseg, d_idat, d_qdat)) return bad;
+        if (const int bad = args::audio_batch(where, d_pcm, pcm_stride, nsamp, nseg, d_idat, d_qdat)) return bad;
         return Context::get().audio_device(d_pcm, pcm_stride, nsamp, nseg, (float*)d_idat, (float*)d_qdat, normalise);
-    } catch (const std::exception& e) { return fail("wspr_audio_batch_device", e); }
-}
-
-int wspr_audio_to_iq(const int16_t* pcm, size_t nsamp, float* I, float* Q, uint32_t* n_out, int normalise) {
-    LaneTurn lane_turn;
-    try {
-        if (nsamp > (size_t)AUDIO_FRONT_MAX_SAMPLES) return audio_args_bad("wspr_audio_to_iq", nullptr, 0, (long long)AUDIO_FRONT_MAX_SAMPLES + 1, 0, nullptr, nullptr);
-        if ((!pcm && nsamp) || !I || !Q) { fprintf(stderr, "libwspr_mi355x: wspr_audio_to_iq: no record, or no output rows\n"); return -1; }
-        Context& c = Context::get();
-        int16_t* d_pcm = c.audio_pcm(nsamp);
-        if (nsamp) HIP_TRY(hipMemcpy(d_pcm, pcm, nsamp * sizeof(int16_t), hipMemcpyHostToDevice));
-        float* wi = c.work_i(1);
-        float* wq = c.work_q(1);
-        const int rc = c.audio_device(d_pcm, (nsamp + 7) & ~(size_t)7, (int)nsamp, 1, wi, wq, normalise);
-        if (rc) return rc;
-        const size_t bytes = (size_t)wspr::kMaxSamples * sizeof(float);
-        std::vector<float> oi(wspr::kMaxSamples), oq(wspr::kMaxSamples);    // both rails arrive before either is handed over
-        HIP_TRY(hipMemcpy(oi.data(), wi, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(oq.data(), wq, bytes, hipMemcpyDeviceToHost));
-        std::memcpy(I, oi.data(), bytes);
-        std::memcpy(Q, oq.data(), bytes);
-        if (n_out) *n_out = (uint32_t)audio_front_n_out((int)nsamp);
-        return 0;
-    } catch (const std::exception& e) { return fail("wspr_audio_to_iq", e); }
-}
-
-// ---- K15, the impulse-noise blanker in front of K12 (kernels/audio_blank.h) -------------------------------------------
-static int blank_settings_bad(const char* where, int thr16, int guard) {
-    if (audio_blank_settings_ok(thr16, guard)) return 0;
-    fprintf(stderr, "libwspr_mi355x: %s: thr16 must be 16 .. 4096 and guard 0 .. 64\n", where);
-    return -1;
+    } catch (const std::exception& e) { return fail(where, e); }
 }
 
 int wspr_audio_blank_batch_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, void* d_out,
@@ -186,20 +140,8 @@ int wspr_audio_blank_batch_device(const void* d_pcm, size_t pcm_stride, int nsam
     static const char* where = "wspr_audio_blank_batch_device";
     LaneTurn lane_turn;
     try {
-        if (const int bad = blank_settings_bad(where, thr16, guard)) return bad;
-        // (the counts' and the input's checks are K12's: its output checks see the input again and pass)
-        if (const int bad = audio_args_bad(where, d_pcm, pcm_stride, nsamp, nseg, d_pcm, d_pcm)) return bad;
+        if (const int bad = args::audio_blank_batch(where, d_pcm, pcm_stride, nsamp, nseg, thr16, guard, d_out, out_stride)) return bad;
         if (nseg == 0) return 0;
-        const char* why = nullptr;
-        const size_t padded = ((size_t)nsamp + 7) & ~(size_t)7;
-        const uintptr_t in0 = reinterpret_cast<uintptr_t>(d_pcm), out0 = reinterpret_cast<uintptr_t>(d_out);
-        const uintptr_t in1 = in0 + (((size_t)nseg - 1) * pcm_stride + padded) * sizeof(int16_t);
-        const uintptr_t out1 = out0 + (((size_t)nseg - 1) * out_stride + padded) * sizeof(int16_t);
-        if (!d_out || (out0 & 15)) why = "d_out must be 16-byte aligned device memory";
-        else if ((out_stride & 7) || out_stride < (size_t)nsamp) why = "out_stride must be a multiple of 8 and at least nsamp";
-        // in place is a race: a neighbouring block's halo would read samples that are already blanked
-        else if (nsamp > 0 && in0 < out1 && out0 < in1) why = "the output rows overlap the input rows";
-        if (why) { fprintf(stderr, "libwspr_mi355x: %s: %s\n", where, why); return -1; }
         return Context::get().audio_blank_device(d_pcm, pcm_stride, nsamp, nseg, thr16, guard, d_out, out_stride, n_blanked);
     } catch (const std::exception& e) { return fail(where, e); }
 }
@@ -209,39 +151,44 @@ int wspr_audio_blanked_batch_device(const void* d_pcm, size_t pcm_stride, int ns
     static const char* where = "wspr_audio_blanked_batch_device";
     LaneTurn lane_turn;
     try {
-        if (const int bad = blank_settings_bad(where, thr16, guard)) return bad;
-        if (const int bad = audio_args_bad(where, d_pcm, pcm_stride, nsamp, nseg, d_idat, d_qdat)) return bad;
+        if (const int bad = args::audio_blanked_batch(where, d_pcm, pcm_stride, nsamp, nseg, thr16, guard, d_idat, d_qdat)) return bad;
         return Context::get().audio_blanked_device(d_pcm, pcm_stride, nsamp, nseg, thr16, guard, (float*)d_idat, (float*)d_qdat,
                                                    normalise, n_blanked);
     } catch (const std::exception& e) { return fail(where, e); }
 }
 
-int wspr_audio_to_iq_blanked(const int16_t* pcm, size_t nsamp, int thr16, int guard, float* I, float* Q, uint32_t* n_out,
-                             int normalise, int* n_blanked) {
-    static const char* where = "wspr_audio_to_iq_blanked";
-    LaneTurn lane_turn;
+// wspr_audio_to_iq() and, with blank = (thr16, guard), wspr_audio_to_iq_blanked(): one record through the context's scratch
+static int audio_to_iq(const char* where, const int16_t* pcm, size_t nsamp, const int* blank, float* I, float* Q, uint32_t* n_out,
+                       int normalise, int* n_blanked) {
     try {
-        if (const int bad = blank_settings_bad(where, thr16, guard)) return bad;
-        if (nsamp > (size_t)AUDIO_FRONT_MAX_SAMPLES) return audio_args_bad(where, nullptr, 0, (long long)AUDIO_FRONT_MAX_SAMPLES + 1, 0, nullptr, nullptr);
-        if ((!pcm && nsamp) || !I || !Q) { fprintf(stderr, "libwspr_mi355x: %s: no record, or no output rows\n", where); return -1; }
+        if (const int bad = args::audio_host(where, pcm, nsamp, blank, I, Q)) return bad;
         Context& c = Context::get();
         int16_t* d_pcm = c.audio_pcm(nsamp);
         if (nsamp) HIP_TRY(hipMemcpy(d_pcm, pcm, nsamp * sizeof(int16_t), hipMemcpyHostToDevice));
         float* wi = c.work_i(1);
         float* wq = c.work_q(1);
+        const size_t stride = (nsamp + 7) & ~(size_t)7;
         int blanked = 0;
-        const int rc = c.audio_blanked_device(d_pcm, (nsamp + 7) & ~(size_t)7, (int)nsamp, 1, thr16, guard, wi, wq, normalise, &blanked);
+        const int rc = blank ? c.audio_blanked_device(d_pcm, stride, (int)nsamp, 1, blank[0], blank[1], wi, wq, normalise, &blanked)
+                             : c.audio_device(d_pcm, stride, (int)nsamp, 1, wi, wq, normalise);
         if (rc) return rc;
-        const size_t bytes = (size_t)wspr::kMaxSamples * sizeof(float);
-        std::vector<float> oi(wspr::kMaxSamples), oq(wspr::kMaxSamples);    // both rails arrive before either is handed over
-        HIP_TRY(hipMemcpy(oi.data(), wi, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(oq.data(), wq, bytes, hipMemcpyDeviceToHost));
-        std::memcpy(I, oi.data(), bytes);
-        std::memcpy(Q, oq.data(), bytes);
+        rows_down(I, Q, wi, wq);
         if (n_out) *n_out = (uint32_t)audio_front_n_out((int)nsamp);
         if (n_blanked) *n_blanked = blanked;
         return 0;
     } catch (const std::exception& e) { return fail(where, e); }
+}
+
+int wspr_audio_to_iq(const int16_t* pcm, size_t nsamp, float* I, float* Q, uint32_t* n_out, int normalise) {
+    LaneTurn lane_turn;
+    return audio_to_iq("wspr_audio_to_iq", pcm, nsamp, nullptr, I, Q, n_out, normalise, nullptr);
+}
+
+int wspr_audio_to_iq_blanked(const int16_t* pcm, size_t nsamp, int thr16, int guard, float* I, float* Q, uint32_t* n_out,
+                             int normalise, int* n_blanked) {
+    LaneTurn lane_turn;
+    const int blank[2] = {thr16, guard};
+    return audio_to_iq("wspr_audio_to_iq_blanked", pcm, nsamp, blank, I, Q, n_out, normalise, n_blanked);
 }
 
 void wspr_audio_constants(float* taps_i511, float* taps_q511, int* samples_per_output) {

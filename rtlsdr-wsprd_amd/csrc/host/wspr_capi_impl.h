@@ -1,8 +1,10 @@
 // What more than one entry-point family of the C ABI (wspr_capi_*.hip) uses: error reporting, the turn a call takes
-// on its (device, lane), device scratch.  Internal: not part of any interface.
+// on its (device, lane), device scratch, the bounce of one row pair or record between the caller and the context's
+// scratch.  Internal: not part of any interface.
 #pragma once
 #include <algorithm>
 #include <cstdio>
+#include <cstring>
 #include <exception>
 #include <mutex>
 #include <stdexcept>
@@ -65,5 +67,27 @@ struct TempDev {
     TempDev& operator=(const TempDev&) = delete;
     template <class T> T* as() { return static_cast<T*>(p); }
 };
+// One row pair or one record between the caller's host memory and the context's scratch (the single-segment forms of the
+// stage calls).  Down, the whole result arrives in memory of the call's own before any of it is handed over: a call
+// that fails has written nothing.
+inline void rows_up(float* wi, float* wq, const float* I, const float* Q, size_t n) {
+    if (!n) return;
+    HIP_TRY(hipMemcpy(wi, I, n * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(wq, Q, n * sizeof(float), hipMemcpyHostToDevice));
+}
+inline void rows_down(float* I, float* Q, const float* wi, const float* wq) {
+    const size_t bytes = (size_t)kMaxSamples * sizeof(float);
+    std::vector<float> oi(kMaxSamples), oq(kMaxSamples);
+    HIP_TRY(hipMemcpy(oi.data(), wi, bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(oq.data(), wq, bytes, hipMemcpyDeviceToHost));
+    std::memcpy(I, oi.data(), bytes);
+    std::memcpy(Q, oq.data(), bytes);
+}
+inline void record_down(int16_t* pcm, const int16_t* d_pcm, size_t nsamp) {
+    if (!nsamp) return;
+    std::vector<int16_t> out(nsamp);
+    HIP_TRY(hipMemcpy(out.data(), d_pcm, nsamp * sizeof(int16_t), hipMemcpyDeviceToHost));
+    std::memcpy(pcm, out.data(), nsamp * sizeof(int16_t));
+}
 }  // namespace capi
 }  // namespace wspr

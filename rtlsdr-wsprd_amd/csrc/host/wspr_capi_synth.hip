@@ -9,135 +9,25 @@
 #include <vector>
 
 #include "wspr_capi_impl.h"
-#include "wspr_context_impl.h"
-#include "../kernels/fade.h"
+#include "wspr_stage_args.h"
 
 using wspr::Context;
 using namespace wspr::capi;
+namespace args = wspr::args;
 
 static_assert(sizeof(wspr_synth_channel) == 24 && sizeof(wspr_synth_path) == 12, "public channel layout");
 static_assert(sizeof(wspr_synth_tx) == 184 && sizeof(wspr_synth_tx) == sizeof(wspr::SynthTx),
               "public and device transmission layouts differ");
 
-namespace wspr {
-
-int Context::synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, float sigma, uint64_t seed,
-                          int flags, float* dI, float* dQ, const FadeChannel* fade) {
-    Impl& c = *d;
-    if (nseg <= 0) return 0;
-    const hipStream_t st = c.stream;
-    std::vector<int> off((size_t)nseg + 1, 0);                 // the list is sorted by seg: offsets per segment
-    for (int t = 0; t < ntx; ++t) ++off[(size_t)tx[t].seg + 1];
-    for (int s = 0; s < nseg; ++s) off[(size_t)s + 1] += off[s];
-    int* d_off = static_cast<int*>(c.synthoff.need(off.size() * sizeof(int)));
-    upload(d_off, off.data(), off.size() * sizeof(int), st);
-    SynthTx* d_tx = nullptr;
-    double* d_ckpt = nullptr;
-    int* d_first = nullptr;
-    if (ntx > 0) {
-        d_tx = static_cast<SynthTx*>(c.synthtx.need((size_t)ntx * sizeof(SynthTx)));
-        d_first = static_cast<int*>(c.synthfirst.need((size_t)ntx * sizeof(int)));
-        d_ckpt = static_cast<double*>(c.synthckpt.need(synth_checkpoint_doubles(ntx) * sizeof(double)));
-        upload(d_tx, tx, (size_t)ntx * sizeof(SynthTx), st);
-    }
-    if (fade) {
-        FadeChannel* d_fade = nullptr;
-        if (ntx > 0) {
-            d_fade = static_cast<FadeChannel*>(c.synthfade.need((size_t)ntx * sizeof(FadeChannel)));
-            upload(d_fade, fade, (size_t)ntx * sizeof(FadeChannel), st);
-        }
-        launch_synth_faded(d_tx, d_fade, ntx, d_off, nseg, seg_index0, sigma, (unsigned long long)seed,
-                           (flags & kSynthFlagAccumulate) != 0, d_ckpt, d_first, dI, dQ, st);
-    } else {
-        launch_synth(d_tx, ntx, d_off, nseg, seg_index0, sigma, (unsigned long long)seed, (flags & kSynthFlagAccumulate) != 0,
-                     d_ckpt, d_first, dI, dQ, st);
-    }
-    if (flags & kSynthFlagNormalise) launch_normalise(dI, dQ, nullptr, nseg, kMaxSamples, st);   // rtlsdr_wsprd.c:290-305
-    HIP_OK(hipGetLastError());
-    if (c.blocking) {                                          // off / tx are host memory of this call: wait either way
-        HIP_OK(hipEventRecord(c.ev_sync, st));
-        host_wait(c.ev_sync);
-    } else {
-        HIP_OK(hipStreamSynchronize(st));
-    }
-    return 0;
-}
-
-float* Context::synth_rows() { return static_cast<float*>(d->synthrows.need((size_t)2 * kIqStride * sizeof(float))); }
-
-}  // namespace wspr
-
-namespace {
-// Everything that can be wrong with a call, checked before anything is written.  No flag names in the texts: the
-// product binary carries no new macro-style string (tests/test_abi.py).
-bool synth_args_ok(const char* where, const wspr_synth_tx* tx, int ntx, int nseg, float sigma, int flags) {
-    const char* why = nullptr;
-    if (ntx < 0 || nseg < 0) why = "negative count";
-    else if (ntx > 0 && !tx) why = "no transmission list";
-    else if (!std::isfinite(sigma)) why = "noise_sigma is not finite";
-    else if (flags & ~(wspr::kSynthFlagAccumulate | wspr::kSynthFlagNormalise)) why = "unknown flag bit";
-    for (int t = 0; t < ntx && !why; ++t) {
-        const wspr_synth_tx& x = tx[t];
-        if (x.seg < 0 || x.seg >= nseg) why = "seg outside the batch";
-        else if (t > 0 && x.seg < tx[t - 1].seg) why = "list not sorted by seg";
-        else if (!std::isfinite(x.f0) || !std::isfinite(x.t0) || !std::isfinite(x.amp) || !std::isfinite(x.drift))
-            why = "f0, t0, amp or drift is not finite";
-        else if (std::fabs((double)x.f0) + std::fabs((double)x.drift) / 2.0 > wspr::kSynthMaxHz)
-            why = "|f0| + |drift|/2 above 1000 Hz";
-        else
-            for (int i = 0; i < 162; ++i) if (x.symbols[i] > 3) { why = "channel symbol above 3"; break; }
-        if (why) { fprintf(stderr, "libwspr_mi355x: %s: transmission %d: %s\n", where, t, why); return false; }
-    }
-    if (why) { fprintf(stderr, "libwspr_mi355x: %s: %s\n", where, why); return false; }
-    return true;
-}
-// The channels of a faded call, likewise; fills `out` with the constants the kernel takes (fade.h).
-bool fade_args_ok(const char* where, const wspr_synth_channel* ch, int ntx, std::vector<wspr::FadeChannel>& out) {
-    out.resize((size_t)ntx);
-    for (int t = 0; t < ntx; ++t)
-        for (int p = 0; p < 2; ++p) {
-            const wspr_synth_path& a = ch[t].path[p];
-            const char* why = nullptr;
-            if (!std::isfinite(a.gain) || !std::isfinite(a.shift) || !std::isfinite(a.sigma)) why = "gain, shift or sigma is not finite";
-            else if (a.sigma != 0.0f && !(a.sigma >= wspr::kFadeMinSigma && a.sigma <= wspr::kFadeMaxSigma))
-                why = "sigma neither 0 nor within 0.001 .. 10 Hz";
-            else if (std::fabs(a.shift) > wspr::kFadeMaxShift) why = "|shift| above 100 Hz";
-            if (why) { fprintf(stderr, "libwspr_mi355x: %s: transmission %d, path %d: %s\n", where, t, p, why); return false; }
-            out[(size_t)t].path[p] = wspr::fade_path_setup(a.gain, a.shift, a.sigma);
-        }
-    return true;
-}
-}  // namespace
-
-extern "C" {
-
-int wspr_synth_batch_device(const wspr_synth_tx* tx, int ntx, int nseg, int seg_index0, float noise_sigma, uint64_t seed,
-                            int flags, void* d_idat, void* d_qdat) {
-    LaneTurn lane_turn;
+// wspr_synth_batch_device() and, with channels, wspr_synth_faded_batch_device()
+static int synth_batch(const char* where, const wspr_synth_tx* tx, const wspr_synth_channel* ch, int ntx, int nseg, int seg_index0,
+                       float noise_sigma, uint64_t seed, int flags, void* d_idat, void* d_qdat) {
     try {
-        if (!synth_args_ok("wspr_synth_batch_device", tx, ntx, nseg, noise_sigma, flags)) return -1;
-        if (nseg > 0 && (!d_idat || !d_qdat || ((reinterpret_cast<uintptr_t>(d_idat) | reinterpret_cast<uintptr_t>(d_qdat)) & 15))) {
-            fprintf(stderr, "libwspr_mi355x: wspr_synth_batch_device: d_idat and d_qdat must be 16-byte aligned device rows\n");
-            return -1;
-        }
-        return Context::get().synth_device(tx, ntx, nseg, seg_index0, noise_sigma, seed, flags, (float*)d_idat, (float*)d_qdat);
-    } catch (const std::exception& e) { return fail("wspr_synth_batch_device", e); }
-}
-
-int wspr_synth_faded_batch_device(const wspr_synth_tx* tx, const wspr_synth_channel* ch, int ntx, int nseg, int seg_index0,
-                                  float noise_sigma, uint64_t seed, int flags, void* d_idat, void* d_qdat) {
-    LaneTurn lane_turn;
-    try {
-        std::vector<wspr::FadeChannel> fade;
-        if (!synth_args_ok("wspr_synth_faded_batch_device", tx, ntx, nseg, noise_sigma, flags)) return -1;
-        if (ch && !fade_args_ok("wspr_synth_faded_batch_device", ch, ntx, fade)) return -1;
-        if (nseg > 0 && (!d_idat || !d_qdat || ((reinterpret_cast<uintptr_t>(d_idat) | reinterpret_cast<uintptr_t>(d_qdat)) & 15))) {
-            fprintf(stderr, "libwspr_mi355x: wspr_synth_faded_batch_device: d_idat and d_qdat must be 16-byte aligned device rows\n");
-            return -1;
-        }
+        std::vector<wspr::FadeChannel> fade;                   // the constants the kernel takes, one per transmission (fade.h)
+        if (const int bad = args::synth_batch(where, tx, ch, ntx, nseg, noise_sigma, flags, d_idat, d_qdat, fade)) return bad;
         return Context::get().synth_device(tx, ntx, nseg, seg_index0, noise_sigma, seed, flags, (float*)d_idat, (float*)d_qdat,
                                            ch ? fade.data() : nullptr);
-    } catch (const std::exception& e) { return fail("wspr_synth_faded_batch_device", e); }
+    } catch (const std::exception& e) { return fail(where, e); }
 }
 
 // wspr_synth() and wspr_synth_faded(): one segment through the context's working rows
@@ -145,26 +35,30 @@ static int synth_host(const char* where, const wspr_synth_tx* tx, const wspr_syn
                       uint64_t seed, int flags, float* I, float* Q) {
     try {
         std::vector<wspr::FadeChannel> fade;
-        if (!synth_args_ok(where, tx, ntx, 1, noise_sigma, flags)) return -1;
-        if (ch && !fade_args_ok(where, ch, ntx, fade)) return -1;
-        if (!I || !Q) { fprintf(stderr, "libwspr_mi355x: %s: no output rows\n", where); return -1; }
+        if (const int bad = args::synth_host(where, tx, ch, ntx, noise_sigma, flags, I, Q, fade)) return bad;
         Context& c = Context::get();
         float* wi = c.work_i(1);
         float* wq = c.work_q(1);
-        const size_t bytes = (size_t)wspr::kMaxSamples * sizeof(float);
-        if (flags & wspr::kSynthFlagAccumulate) {
-            HIP_TRY(hipMemcpy(wi, I, bytes, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(wq, Q, bytes, hipMemcpyHostToDevice));
-        }
+        if (flags & wspr::kSynthFlagAccumulate) rows_up(wi, wq, I, Q, wspr::kMaxSamples);
         const int rc = c.synth_device(tx, ntx, 1, 0, noise_sigma, seed, flags, wi, wq, ch ? fade.data() : nullptr);
         if (rc) return rc;
-        std::vector<float> oi(wspr::kMaxSamples), oq(wspr::kMaxSamples);    // both rails arrive before either is handed over
-        HIP_TRY(hipMemcpy(oi.data(), wi, bytes, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(oq.data(), wq, bytes, hipMemcpyDeviceToHost));
-        std::memcpy(I, oi.data(), bytes);
-        std::memcpy(Q, oq.data(), bytes);
+        rows_down(I, Q, wi, wq);
         return 0;
     } catch (const std::exception& e) { return fail(where, e); }
+}
+
+extern "C" {
+
+int wspr_synth_batch_device(const wspr_synth_tx* tx, int ntx, int nseg, int seg_index0, float noise_sigma, uint64_t seed,
+                            int flags, void* d_idat, void* d_qdat) {
+    LaneTurn lane_turn;
+    return synth_batch("wspr_synth_batch_device", tx, nullptr, ntx, nseg, seg_index0, noise_sigma, seed, flags, d_idat, d_qdat);
+}
+
+int wspr_synth_faded_batch_device(const wspr_synth_tx* tx, const wspr_synth_channel* ch, int ntx, int nseg, int seg_index0,
+                                  float noise_sigma, uint64_t seed, int flags, void* d_idat, void* d_qdat) {
+    LaneTurn lane_turn;
+    return synth_batch("wspr_synth_faded_batch_device", tx, ch, ntx, nseg, seg_index0, noise_sigma, seed, flags, d_idat, d_qdat);
 }
 
 int wspr_synth(const wspr_synth_tx* tx, int ntx, float noise_sigma, uint64_t seed, int flags, float* I, float* Q) {

@@ -1,10 +1,9 @@
 // Contexts of the MI355X WSPR decoder: one per (device, lane, slot) -- HIP streams, constant tables, grow-only device
-// and pinned buffers, host pools -- and everything that is not the decode itself: how input reaches the working buffers
-// (host rows pageable or pinned, resident rows), the front end's entry points, the single-call stages behind the
-// reference's sync_and_demodulate() / subtract_signal*().  The decode is wspr_pipeline.hip.
+// and pinned buffers, host pools -- how input reaches the working buffers (host rows pageable or pinned, resident rows)
+// and the single-call stages behind the reference's sync_and_demodulate() / subtract_signal*().  The decode is
+// wspr_pipeline.hip; the stage calls (front end, audio, noise figures, synthesisers) are wspr_context_stages.hip.
 #include "wspr_context_impl.h"
 #include "../kernels/glibc_sincosf.h"
-#include "../kernels/noise.h"
 
 namespace wspr {
 
@@ -424,12 +423,7 @@ void Context::store_host(float* I, float* Q, int nseg, int samples, size_t strid
 }
 void Context::sync() {
     HIP_OK(hipGetLastError());
-    if (d->blocking) {
-        HIP_OK(hipEventRecord(d->ev_sync, d->stream));
-        host_wait(d->ev_sync);
-    } else {
-        HIP_OK(hipStreamSynchronize(d->stream));
-    }
+    d->wait(d->stream);
     d->resolve_deferred();
 }
 
@@ -600,231 +594,6 @@ void Context::subtract_symbolwise_single(float* id, float* qd, long np, float f0
     upload(d_sym, sym, kNSymD, c.stream);
     launch_subtract_symbolwise(c.iqI.as<float>(), c.iqQ.as<float>(), samples, f0, shift, drift, d_sym, c.stream);
     store_host(id, qd, 1, samples, (size_t)samples);
-}
-
-// CUs the front end may occupy (0 = all).  K0 is HBM-bound and launches hundreds of thousands of short workgroups:
-// on an unmasked stream they take every CU as it frees up and the decoder's fp32-bound kernels of the other lanes
-// wait.  Confined to a share of the CUs (a stream created with hipExtStreamCreateWithCUMask; consecutive mask bits
-// fall on different XCDs, so the share is spread over all eight and keeps every HBM stack busy), K0 still finds
-// the memory bandwidth it needs while the rest of the chip keeps computing.
-std::atomic<int>& front_end_cus() {
-    static std::atomic<int> v{[] { const char* e = lab_env("WSPR_K0_CUS"); return e ? atoi(e) : 0; }()};
-    return v;
-}
-
-hipStream_t Context::front_end_stream() {
-    Impl& c = *d;
-    const int want = front_end_cus().load();
-    if (want != c.fe_cus) {
-        if (c.fe_stream) { (void)hipStreamSynchronize(c.fe_stream); (void)hipStreamDestroy(c.fe_stream); c.fe_stream = nullptr; }
-        c.fe_cus = want;
-        if (want > 0) {
-            hipDeviceProp_t prop;
-            HIP_OK(hipGetDeviceProperties(&prop, c.device));
-            const int ncu = prop.multiProcessorCount;
-            const int n = std::max(8, std::min(want, ncu));
-            std::vector<uint32_t> mask((ncu + 31) / 32, 0u);
-            for (int i = 0; i < n; ++i) mask[i >> 5] |= 1u << (i & 31);
-            HIP_OK(hipExtStreamCreateWithCUMask(&c.fe_stream, (uint32_t)mask.size(), mask.data()));
-        }
-    }
-    return c.fe_stream ? c.fe_stream : c.stream;
-}
-
-int Context::decimate_device(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int normalise,
-                             int* h_nout, DecimState* d_states) {
-    Impl& c = *d;
-    const hipStream_t st = d_states ? c.stream : front_end_stream();     // whole segments only: streaming chunks are small
-    const size_t nblocks = (size_t)decimate_blocks(bytes_per_seg / 2, d_states != nullptr);
-    if (nblocks == 0) return -1;
-    int32_t* scratch = static_cast<int32_t*>(c.decscratch.need((size_t)nseg * nblocks * 24));
-    int* d_nv = static_cast<int*>(c.nvalid.need((size_t)nseg * 4));
-    if (!d_states) {                                          // whole segments: the unfilled tail must read as zero
-        HIP_OK(hipMemsetAsync(dI, 0, (size_t)nseg * kIqStride * 4, st));
-        HIP_OK(hipMemsetAsync(dQ, 0, (size_t)nseg * kIqStride * 4, st));
-    }
-    launch_decimate(static_cast<const uint8_t*>(d_raw), bytes_per_seg, nseg, dI, dQ, d_nv, scratch, st, d_states);
-    if (normalise) launch_normalise(dI, dQ, d_nv, nseg, kMaxSamples, st);
-    if (h_nout) HIP_OK(hipMemcpyAsync(h_nout, d_nv, (size_t)nseg * 4, hipMemcpyDeviceToHost, st));
-    if (c.blocking) {
-        HIP_OK(hipEventRecord(c.ev_sync, st));
-        host_wait(c.ev_sync);
-    } else {
-        HIP_OK(hipStreamSynchronize(st));
-    }
-    return 0;
-}
-
-// K12: the audio front end on the lane's stream, then (normalise) the receiver's scaling as for the RTL-SDR front end
-int Context::audio_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, float* dI, float* dQ, int normalise) {
-    Impl& c = *d;
-    if (nseg <= 0) return 0;
-    launch_audio_front(static_cast<const int16_t*>(d_pcm), pcm_stride, nsamp, nseg, dI, dQ, c.stream);
-    if (normalise) launch_normalise(dI, dQ, nullptr, nseg, kMaxSamples, c.stream);
-    HIP_OK(hipGetLastError());
-    if (c.blocking) {
-        HIP_OK(hipEventRecord(c.ev_sync, c.stream));
-        host_wait(c.ev_sync);
-    } else {
-        HIP_OK(hipStreamSynchronize(c.stream));
-    }
-    return 0;
-}
-
-// K15: the blanker on the lane's stream; the records' counters come back with it
-int Context::audio_blank_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, void* d_out,
-                                size_t out_stride, int* h_blanked) {
-    Impl& c = *d;
-    if (nseg <= 0) return 0;
-    int* d_count = static_cast<int*>(c.blankcount.need((size_t)nseg * sizeof(int)));
-    HIP_OK(hipMemsetAsync(d_count, 0, (size_t)nseg * sizeof(int), c.stream));
-    launch_audio_blank(static_cast<const int16_t*>(d_pcm), pcm_stride, nsamp, nseg, thr16, guard, static_cast<int16_t*>(d_out),
-                       out_stride, d_count, c.stream);
-    HIP_OK(hipGetLastError());
-    if (h_blanked) HIP_OK(hipMemcpyAsync(h_blanked, d_count, (size_t)nseg * sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    if (c.blocking) {
-        HIP_OK(hipEventRecord(c.ev_sync, c.stream));
-        host_wait(c.ev_sync);
-    } else {
-        HIP_OK(hipStreamSynchronize(c.stream));
-    }
-    return 0;
-}
-
-// K15 then K12, kBlankChunk records at a time through the context's scratch rows (both kernels on the lane's stream, so a
-// chunk's K15 waits for the K12 that still reads the rows): the scratch never exceeds kBlankChunk rows, whatever nseg is
-int Context::audio_blanked_device(const void* d_pcm, size_t pcm_stride, int nsamp, int nseg, int thr16, int guard, float* dI,
-                                  float* dQ, int normalise, int* h_blanked) {
-    Impl& c = *d;
-    if (nseg <= 0) return 0;
-    const size_t row = ((size_t)nsamp + 7) & ~(size_t)7;
-    const size_t bytes = (size_t)std::min(nseg, kBlankChunk) * row * sizeof(int16_t) + 16;
-    if (bytes > c.blankrows.cap) {                            // exactly what is needed: need() would add a quarter to 369 MB
-        c.blankrows.release();
-        HIP_OK(hipMalloc(&c.blankrows.p, bytes));
-        c.blankrows.cap = bytes;
-    }
-    int16_t* rows = c.blankrows.as<int16_t>();
-    int* d_count = static_cast<int*>(c.blankcount.need((size_t)nseg * sizeof(int)));
-    HIP_OK(hipMemsetAsync(d_count, 0, (size_t)nseg * sizeof(int), c.stream));
-    const int16_t* in = static_cast<const int16_t*>(d_pcm);
-    for (int s0 = 0; s0 < nseg; s0 += kBlankChunk) {
-        const int n = std::min(kBlankChunk, nseg - s0);
-        launch_audio_blank(in + (size_t)s0 * pcm_stride, pcm_stride, nsamp, n, thr16, guard, rows, row, d_count + s0, c.stream);
-        launch_audio_front(rows, row, nsamp, n, dI + (size_t)s0 * kIqStride, dQ + (size_t)s0 * kIqStride, c.stream);
-    }
-    if (normalise) launch_normalise(dI, dQ, nullptr, nseg, kMaxSamples, c.stream);
-    HIP_OK(hipGetLastError());
-    if (h_blanked) HIP_OK(hipMemcpyAsync(h_blanked, d_count, (size_t)nseg * sizeof(int), hipMemcpyDeviceToHost, c.stream));
-    if (c.blocking) {
-        HIP_OK(hipEventRecord(c.ev_sync, c.stream));
-        host_wait(c.ev_sync);
-    } else {
-        HIP_OK(hipStreamSynchronize(c.stream));
-    }
-    return 0;
-}
-
-// K16 on the lane's stream; the records come back with it.  The table is built on first use: a process that never asks
-// for the figures allocates nothing for them.
-int Context::noise_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, const noise::Windows& win,
-                          noise::Result* out) {
-    Impl& c = *d;
-    if (nseg <= 0) return 0;
-    if (!c.noise_tab.p) {
-        std::vector<float> host(noise::kTableFloats);
-        const double w2 = noise::noise_tables(host.data());
-        float* p = static_cast<float*>(c.noise_tab.need(host.size() * sizeof(float)));
-        HIP_OK(hipMemcpy(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-        c.noise_w2 = w2;
-    }
-    const size_t bytes = (size_t)nseg * sizeof(noise::Result);
-    void* d_out = c.noise_out.need(bytes);
-    noise::Result* h_out = static_cast<noise::Result*>(c.h_noise.need(bytes));
-    launch_noise(dI, dQ, samples, stride, nseg, c.noise_tab.as<float>(), c.noise_w2, win, d_out, c.stream);
-    HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(h_out, d_out, bytes, hipMemcpyDeviceToHost, c.stream));
-    if (c.blocking) {
-        HIP_OK(hipEventRecord(c.ev_sync, c.stream));
-        host_wait(c.ev_sync);
-    } else {
-        HIP_OK(hipStreamSynchronize(c.stream));
-    }
-    memcpy(out, h_out, bytes);                               // every record has arrived before the first is handed over
-    return 0;
-}
-
-int16_t* Context::audio_pcm(size_t nsamp) { return static_cast<int16_t*>(d->audiopcm.need(((nsamp + 7) & ~(size_t)7) * 2 + 16)); }
-
-// one chunk of one receiver's stream: state in, appended outputs and state out (host buffers)
-int Context::decimate_stream(DecimState* h_state, const uint8_t* iq, size_t nbytes, float* I, float* Q, uint32_t fill,
-                             uint32_t cap, uint32_t* new_fill) {
-    Impl& c = *d;
-    if (nbytes == 0) { if (new_fill) *new_fill = fill; return 0; }
-    uint8_t* d_raw = static_cast<uint8_t*>(c.streamraw.need(nbytes + 16));
-    DecimState* d_st = static_cast<DecimState*>(c.streamstate.need(sizeof(DecimState)));
-    upload(d_raw, iq, nbytes, c.stream);
-    upload(d_st, h_state, sizeof(DecimState), c.stream);
-    float* wi = work_i(1);
-    float* wq = work_q(1);
-    int nout = 0;
-    const int rc = decimate_device(d_raw, nbytes, 1, wi, wq, 0, &nout, d_st);
-    if (rc) return rc;
-    HIP_OK(hipMemcpy(h_state, d_st, sizeof(DecimState), hipMemcpyDeviceToHost));
-    const uint32_t room = fill < cap ? cap - fill : 0u;
-    const uint32_t take = std::min<uint32_t>((uint32_t)nout, room);       // outputs beyond the capacity are dropped
-    if (take) {                                                            // (rtlsdr_wsprd.c:236-242)
-        HIP_OK(hipMemcpy(I + fill, wi, (size_t)take * 4, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(Q + fill, wq, (size_t)take * 4, hipMemcpyDeviceToHost));
-    }
-    if (new_fill) *new_fill = fill + take;
-    return 0;
-}
-
-// One chunk of each of n receivers' streams: what n calls of decimate_stream() do, as ONE host-to-device transfer, one
-// launch set over n rows with n carried states, and three transfers back (states, the rows' first outputs per rail).
-// A callback of 65 536 bytes yields five or six samples: its cost is the round trips, not the arithmetic.
-int Context::decimate_stream_many(DecimState* const* h_states, const uint8_t* const* iq, size_t nbytes, int n, float* const* I,
-                                  float* const* Q, const uint32_t* fill, uint32_t cap, uint32_t* new_fill) {
-    Impl& c = *d;
-    if (n <= 0 || nbytes == 0) { for (int k = 0; k < n; ++k) new_fill[k] = fill[k]; return 0; }
-    const int maxout = (int)(nbytes / 2 / 6401) + 2;                       // outputs a chunk of this size can yield
-    const size_t ocols = (size_t)((maxout + 3) & ~3);
-    uint8_t* h_raw = static_cast<uint8_t*>(c.h_streamraw.need((size_t)n * nbytes));
-    DecimState* h_st = static_cast<DecimState*>(c.h_streamstate.need((size_t)n * sizeof(DecimState) + (size_t)n * 4));
-    int* h_nout = reinterpret_cast<int*>(h_st + n);
-    float* h_out = static_cast<float*>(c.h_streamout.need(2 * (size_t)n * ocols * 4));
-    for (int k = 0; k < n; ++k) {
-        memcpy(h_raw + (size_t)k * nbytes, iq[k], nbytes);
-        h_st[k] = *h_states[k];
-    }
-    uint8_t* d_raw = static_cast<uint8_t*>(c.streamraw.need((size_t)n * nbytes + 16));
-    DecimState* d_st = static_cast<DecimState*>(c.streamstate.need((size_t)n * sizeof(DecimState)));
-    HIP_OK(hipMemcpyAsync(d_raw, h_raw, (size_t)n * nbytes, hipMemcpyHostToDevice, c.stream));
-    HIP_OK(hipMemcpyAsync(d_st, h_st, (size_t)n * sizeof(DecimState), hipMemcpyHostToDevice, c.stream));
-    float* wi = work_i(n);
-    float* wq = work_q(n);
-    const size_t nblocks = (size_t)decimate_blocks(nbytes / 2, true);
-    if (nblocks == 0) return -1;
-    int32_t* scratch = static_cast<int32_t*>(c.decscratch.need((size_t)n * nblocks * 24));
-    int* d_nv = static_cast<int*>(c.nvalid.need((size_t)n * 4));
-    launch_decimate(d_raw, nbytes, n, wi, wq, d_nv, scratch, c.stream, d_st);
-    HIP_OK(hipMemcpyAsync(h_nout, d_nv, (size_t)n * 4, hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpyAsync(h_st, d_st, (size_t)n * sizeof(DecimState), hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpy2DAsync(h_out, ocols * 4, wi, (size_t)kIqStride * 4, ocols * 4, n, hipMemcpyDeviceToHost, c.stream));
-    HIP_OK(hipMemcpy2DAsync(h_out + (size_t)n * ocols, ocols * 4, wq, (size_t)kIqStride * 4, ocols * 4, n, hipMemcpyDeviceToHost, c.stream));
-    sync();
-    for (int k = 0; k < n; ++k) {
-        *h_states[k] = h_st[k];
-        const uint32_t room = fill[k] < cap ? cap - fill[k] : 0u;
-        const uint32_t take = std::min<uint32_t>((uint32_t)std::max(0, std::min(h_nout[k], maxout)), room);   // beyond the capacity: dropped
-        if (take) {                                                                          // (rtlsdr_wsprd.c:236-242)
-            memcpy(I[k] + fill[k], h_out + (size_t)k * ocols, (size_t)take * 4);
-            memcpy(Q[k] + fill[k], h_out + (size_t)n * ocols + (size_t)k * ocols, (size_t)take * 4);
-        }
-        new_fill[k] = fill[k] + take;
-    }
-    return 0;
 }
 
 }  // namespace wspr

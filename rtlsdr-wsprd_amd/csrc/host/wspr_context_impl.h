@@ -1,6 +1,7 @@
-// Internals shared by the two translation units of the host scheduler (wspr_context.hip: contexts, lanes, buffers,
-// loads, front end, single-call stages; wspr_pipeline.hip: the decode itself): how a host thread waits, grow-only
-// buffers, the fork-join pool, the context's state, the CPUs a rank may count on.  Not part of any interface.
+// Internals shared by the three translation units of the host scheduler (wspr_context.hip: contexts, lanes, buffers,
+// loads, single-call decode stages; wspr_context_stages.hip: the stage calls K0, K8/K13, K12, K15, K16, K17, K18;
+// wspr_pipeline.hip: the decode itself): how a host thread waits, grow-only buffers, the fork-join pool, the context's
+// state, the CPUs a rank may count on.  Not part of any interface.
 #pragma once
 #include "wspr_pipeline.h"
 
@@ -294,6 +295,15 @@ struct Context::Impl {
     void count_fano(int ret, unsigned cycles) { n_fano++; n_cycles += cycles; if (ret) n_timeout++; }
     bool blocking = false;
     hipEvent_t ev_sync = nullptr;
+    // the host waits until `st` has done everything queued so far, by the context's way of waiting (host_wait() above)
+    void wait(hipStream_t st) {
+        if (blocking) {
+            HIP_OK(hipEventRecord(ev_sync, st));
+            host_wait(ev_sync);
+        } else {
+            HIP_OK(hipStreamSynchronize(st));
+        }
+    }
     hipEvent_t ev[2] = {nullptr, nullptr};
     // spans timed without a host wait: event pairs recorded around the launches, read back after a later
     // synchronisation of the same (in-order) stream has passed them

@@ -253,17 +253,18 @@ public:
     int noise_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, const noise::Windows& win,
                      noise::Result* out);
 
-    // K8 (wspr_capi_synth.hip): a validated, sorted transmission list into nseg device rows; complete on return
+    // The stage calls below are wspr_context_stages.hip; their arguments have been validated (wspr_stage_args.h).
+    // K8 (k8_synth.hip): a validated, sorted transmission list into nseg device rows; complete on return
     // fade: one FadeChannel (kernels/fade.h) per transmission in host memory for the fading channel (K13), or null (K8)
     int synth_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, float sigma, uint64_t seed,
                      int flags, float* dI, float* dQ, const FadeChannel* fade = nullptr);
     float* synth_rows();            // two rows of kIqStride floats of the context's own (wspr_selftest)
-    // K17 (wspr_capi_audio_synth.hip; the definition in kernels/audio_synth.h): a validated, sorted transmission list into
+    // K17 (k17_audio_synth.hip; the definition in kernels/audio_synth.h): a validated, sorted transmission list into
     // nseg validated device records of nsamp 16-bit samples; h_clipped (nseg, may be null) = samples clipped of each;
     // complete on return
     int synth_audio_device(const wspr_synth_tx* tx, int ntx, int nseg, long long seg_index0, int nsamp, float sigma,
                            uint64_t seed, int flags, int16_t* d_pcm, size_t pcm_stride, int* h_clipped);
-    // K18 (wspr_capi_iq_audio.hip; the definition in kernels/iq_audio.h): nseg validated device rows of `samples` samples into
+    // K18 (k18_iq_audio.hip; the definition in kernels/iq_audio.h): nseg validated device rows of `samples` samples into
     // nseg validated device records of 32 * samples 16-bit samples; h_clipped (nseg, may be null) = samples clipped of each;
     // complete on return
     int iq_audio_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, float gain, int16_t* d_pcm,

@@ -35,6 +35,7 @@
 #pragma once
 #include <stdint.h>
 
+#include "pcm_quantise.h"
 #include "synth_math.h"
 
 namespace wspr {
@@ -76,11 +77,6 @@ WSPR_HD int audio_synth_first(float t0) {
                                              : (q < -(double)kAudioSynthFirstClamp ? -kAudioSynthFirstClamp : (int)q);
 }
 // step 4; *clipped is incremented for a sample that leaves the 16-bit range
-WSPR_HD int16_t audio_synth_quantise(double acc, int* clipped) {
-    const double magic = 6755399441055744.0;               // 1.5 * 2^52: (t + magic) - magic = t rounded to an integer, ties to even
-    if (acc > 32767.0) { ++*clipped; return (int16_t)32767; }
-    if (acc < -32768.0) { ++*clipped; return (int16_t)-32768; }
-    return (int16_t)(int)((acc + magic) - magic);
-}
+WSPR_HD int16_t audio_synth_quantise(double acc, int* clipped) { return pcm_quantise(acc, clipped); }
 
 }  // namespace wspr

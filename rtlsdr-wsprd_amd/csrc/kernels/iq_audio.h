@@ -16,9 +16,8 @@
  *   p = (double)y * (double)gain
  *   p is NaN:   the sample is 0 and counts as clipped
  *   otherwise:  p > 32767.0 gives 32767, p < -32768.0 gives -32768, and either counts as clipped; else the sample is
- *               (p + 6755399441055744.0) - 6755399441055744.0 -- nearest, ties to even.  This is audio_synth_quantise() of
- *               audio_synth.h (K17), stated again here because that header is C++ and this one is not;
- *               tests/test_iq_audio_checker.py holds the two to each other.
+ *               (p + 6755399441055744.0) - 6755399441055744.0 -- nearest, ties to even: pcm_quantise() of pcm_quantise.h,
+ *               which K17's audio_synth_quantise() is as well.
  * fmaf is the single rounding rule of the chain and nothing else is fused or reordered (-ffp-contract=off on both sides).
  *
  * THE SKIPPED STEPS ARE PART OF THE DEFINITION.  gI[k] for k = 2, 6 (mod 8) and gQ[k] for k = 0, 4 (mod 8) are +0.0f
@@ -40,6 +39,7 @@
 #include <stdint.h>
 
 #include "audio_front.h"
+#include "pcm_quantise.h"
 
 #define IQ_AUDIO_INTERP      AUDIO_FRONT_DECIM      /* output samples per input sample */
 #define IQ_AUDIO_MAX_SAMPLES AUDIO_FRONT_MAX_OUT    /* inputs of a row: 45 000 */
@@ -62,11 +62,8 @@ IQ_AUDIO_CONSTEXPR IQ_AUDIO_HD int iq_audio_skipped(int rail, int k) {
 
 /* the last three lines of the definition; *clipped is incremented for a sample that leaves the 16-bit range or is NaN */
 IQ_AUDIO_HD int16_t iq_audio_quantise(double p, int *clipped) {
-    const double magic = 6755399441055744.0;                /* 1.5 * 2^52 */
     if (p != p) { ++*clipped; return (int16_t)0; }
-    if (p > 32767.0) { ++*clipped; return (int16_t)32767; }
-    if (p < -32768.0) { ++*clipped; return (int16_t)-32768; }
-    return (int16_t)(int)((p + magic) - magic);
+    return pcm_quantise(p, clipped);
 }
 IQ_AUDIO_HD int16_t iq_audio_sample(float acc, float gain, int *clipped) {
     const float y = 16.0f * acc;

@@ -18,17 +18,15 @@
 #include <hip/hip_runtime.h>
 
 #include "fade.h"
-#include "wspr_device.h"
+#include "synth_tile.h"
 
 namespace wspr {
 
 static_assert(sizeof(FadeChannel) == 64, "FadeChannel is 64 bytes");
 
 namespace {
-constexpr int kPerThread = 16;
-constexpr int kTile = 256 * kPerThread;                   // 4 096 samples; 11 tiles cover a row of kIqStride floats
+constexpr int kPerThread = kSynthPerThread, kTile = kSynthTile;   // 16 samples per thread, tiles of 4 096 (synth_tile.h)
 constexpr int kMaxTaps = kTile / 4 + kFadeTerms;          // 1 040: L >= 4 (sigma <= 10 Hz, refused above that)
-static_assert(kIqStride % kTile == 0, "tiles must cover the row exactly");
 
 __global__ __launch_bounds__(256)
 void synth_fade_kernel(const SynthTx* __restrict__ tx, const FadeChannel* __restrict__ ch, int ntx,
@@ -42,24 +40,8 @@ void synth_fade_kernel(const SynthTx* __restrict__ tx, const FadeChannel* __rest
     float4* __restrict__ pi = reinterpret_cast<float4*>(dI + (size_t)seg * kIqStride + base);
     float4* __restrict__ pq = reinterpret_cast<float4*>(dQ + (size_t)seg * kIqStride + base);
     float xi[kPerThread], xq[kPerThread];
-#pragma unroll
-    for (int v = 0; v < kPerThread / 4; ++v) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-        if (accumulate) { a = pi[v]; b = pq[v]; }
-        xi[4 * v] = a.x; xi[4 * v + 1] = a.y; xi[4 * v + 2] = a.z; xi[4 * v + 3] = a.w;
-        xq[4 * v] = b.x; xq[4 * v + 1] = b.y; xq[4 * v + 2] = b.z; xq[4 * v + 3] = b.w;
-    }
-    if (sigma > 0.0f) {
-#pragma unroll
-        for (int s = 0; s < kPerThread; ++s) {
-            if (base + s < kMaxSamples) {
-                float nI, nQ;
-                synth_noise(seed, seg_index0 + seg, base + s, sigma, &nI, &nQ);
-                xi[s] = (float)((double)xi[s] + (double)nI);
-                xq[s] = (float)((double)xq[s] + (double)nQ);
-            }
-        }
-    }
+    synth_tile_load(pi, pq, accumulate, xi, xq);
+    synth_tile_noise(seed, seg_index0 + seg, base, sigma, xi, xq);
     const int t_begin = seg_off[seg], t_end = seg_off[seg + 1];
     for (int t = t_begin; t < t_end; ++t) {                             // uniform over the workgroup
         const int f = first[t];
@@ -85,10 +67,8 @@ void synth_fade_kernel(const SynthTx* __restrict__ tx, const FadeChannel* __rest
         const float f0 = me->f0, drift = me->drift;
         const double amp = (double)me->amp;
         const int nlo = n0 < 0 ? 0 : n0;
-        const int ck = nlo / kSynthCkptEvery;
-        double phi = ckpt[(size_t)ck * ntx + t];
-        double dphi = synth_dphi(f0, drift, nlo >> 8, me->symbols[nlo >> 8]);
-        for (int m = ck * kSynthCkptEvery; m < nlo; ++m) phi += dphi;   // same symbol: 64 divides 256
+        double dphi;
+        double phi = synth_phase_at(me, ckpt, ntx, t, nlo, &dphi);
 #pragma unroll
         for (int s = 0; s < kPerThread; ++s) {
             const int n = n0 + s;
@@ -118,11 +98,7 @@ void synth_fade_kernel(const SynthTx* __restrict__ tx, const FadeChannel* __rest
             }
         }
     }
-#pragma unroll
-    for (int v = 0; v < kPerThread / 4; ++v) {
-        pi[v] = make_float4(xi[4 * v], xi[4 * v + 1], xi[4 * v + 2], xi[4 * v + 3]);
-        pq[v] = make_float4(xq[4 * v], xq[4 * v + 1], xq[4 * v + 2], xq[4 * v + 3]);
-    }
+    synth_tile_store(pi, pq, xi, xq);
 }
 }  // namespace
 

@@ -18,8 +18,7 @@
 // 18 sine kernel, 22 cosine kernel, 4 for the two rails, 1 phase add) and four float/double conversions.
 #include <hip/hip_runtime.h>
 
-#include "synth_math.h"
-#include "wspr_device.h"
+#include "synth_tile.h"
 
 namespace wspr {
 
@@ -28,9 +27,7 @@ static_assert(kSynthSamples == kMaxSamples && kSynthSigLen == kSigLen, "synth_ma
 namespace {
 constexpr int kCkptEvery = kSynthCkptEvery;               // 64
 constexpr int kCkptPerTx = kSigLen / kCkptEvery;          // 648
-constexpr int kPerThread = 16;
-constexpr int kTile = 256 * kPerThread;                   // 4 096 samples; 11 tiles cover a row of kIqStride floats
-static_assert(kIqStride % kTile == 0, "tiles must cover the row exactly");
+constexpr int kPerThread = kSynthPerThread, kTile = kSynthTile;   // 16 samples per thread, tiles of 4 096 (synth_tile.h)
 
 __global__ __launch_bounds__(64)
 void synth_phase_kernel(const SynthTx* __restrict__ tx, int ntx, double* __restrict__ ckpt, int* __restrict__ first) {
@@ -59,24 +56,8 @@ void synth_fill_kernel(const SynthTx* __restrict__ tx, int ntx, const int* __res
     float4* __restrict__ pi = reinterpret_cast<float4*>(dI + (size_t)seg * kIqStride + base);
     float4* __restrict__ pq = reinterpret_cast<float4*>(dQ + (size_t)seg * kIqStride + base);
     float xi[kPerThread], xq[kPerThread];
-#pragma unroll
-    for (int v = 0; v < kPerThread / 4; ++v) {
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f), b = a;
-        if (accumulate) { a = pi[v]; b = pq[v]; }
-        xi[4 * v] = a.x; xi[4 * v + 1] = a.y; xi[4 * v + 2] = a.z; xi[4 * v + 3] = a.w;
-        xq[4 * v] = b.x; xq[4 * v + 1] = b.y; xq[4 * v + 2] = b.z; xq[4 * v + 3] = b.w;
-    }
-    if (sigma > 0.0f) {
-#pragma unroll
-        for (int s = 0; s < kPerThread; ++s) {
-            if (base + s < kMaxSamples) {
-                float nI, nQ;
-                synth_noise(seed, seg_index0 + seg, base + s, sigma, &nI, &nQ);
-                xi[s] = (float)((double)xi[s] + (double)nI);
-                xq[s] = (float)((double)xq[s] + (double)nQ);
-            }
-        }
-    }
+    synth_tile_load(pi, pq, accumulate, xi, xq);
+    synth_tile_noise(seed, seg_index0 + seg, base, sigma, xi, xq);
     const int t_end = seg_off[seg + 1];
     for (int t = seg_off[seg]; t < t_end; ++t) {
         const int n0 = base - first[t];                    // the transmission's sample index at this thread's first output
@@ -85,10 +66,8 @@ void synth_fill_kernel(const SynthTx* __restrict__ tx, int ntx, const int* __res
         const float f0 = me->f0, drift = me->drift;
         const double amp = (double)me->amp;
         const int nlo = n0 < 0 ? 0 : n0;
-        const int c = nlo / kCkptEvery;
-        double phi = ckpt[(size_t)c * ntx + t];
-        double dphi = synth_dphi(f0, drift, nlo >> 8, me->symbols[nlo >> 8]);
-        for (int m = c * kCkptEvery; m < nlo; ++m) phi += dphi;          // same symbol: 64 divides 256
+        double dphi;
+        double phi = synth_phase_at(me, ckpt, ntx, t, nlo, &dphi);
 #pragma unroll
         for (int s = 0; s < kPerThread; ++s) {
             const int n = n0 + s;
@@ -102,11 +81,7 @@ void synth_fill_kernel(const SynthTx* __restrict__ tx, int ntx, const int* __res
             }
         }
     }
-#pragma unroll
-    for (int v = 0; v < kPerThread / 4; ++v) {
-        pi[v] = make_float4(xi[4 * v], xi[4 * v + 1], xi[4 * v + 2], xi[4 * v + 3]);
-        pq[v] = make_float4(xq[4 * v], xq[4 * v + 1], xq[4 * v + 2], xq[4 * v + 3]);
-    }
+    synth_tile_store(pi, pq, xi, xq);
 }
 }  // namespace
 

@@ -65,8 +65,8 @@ def test_checker_equals_a_float64_numpy_statement_to_one_lsb():
 
 
 def test_quantiser_is_the_audio_scene_synthesisers():
-    """iq_audio.h states audio_synth_quantise() again (that header is C++): the two agree on every value but NaN, which K17
-    never sees and K18 defines as 0, clipped."""
+    """iq_audio_quantise() and audio_synth_quantise() share their clip-and-round tail (kernels/pcm_quantise.h): the two agree
+    on every value but NaN, which K17 never sees and K18 defines as 0, clipped."""
     rng = np.random.default_rng(5)
     p = np.concatenate((rng.uniform(-40000, 40000, 20000), np.arange(-8, 8) + 0.5, [32767.0, 32767.4, 32767.5, 32767.0000001,
                         -32768.0, -32768.5, -32768.0000001, 1e300, -1e300, np.inf, -np.inf, 0.0, -0.0, 1e-320]))

@@ -1,13 +1,14 @@
 #!/usr/bin/env python3
-"""Compares the gfx950 code of K1, K4 and K7 between two source trees, without a GPU.
+"""Compares the gfx950 code of kernel sources (by default K1, K4 and K7) between two source trees, without a GPU.
 
-Both trees' kernels/k1_fft_bank.hip, k4_demod.hip and k7_subtract.hip are compiled to assembly with build.sh's FLAGS
-(plus --cuda-device-only -S), once plain and once with -DWSPR_LAB.  For every function symbol the opcode histogram
+Both trees' kernels/k1_fft_bank.hip, k4_demod.hip and k7_subtract.hip (or the files named with --sources) are compiled
+to assembly with build.sh's FLAGS (plus --cuda-device-only -S), once plain and once with -DWSPR_LAB.  For every function symbol the opcode histogram
 (mnemonic -> count) and, for kernels, the code-object metadata (vgpr_count, sgpr_count, group_segment_fixed_size,
 private_segment_fixed_size, vgpr_spill_count) are compared.  Register numbers and the order of commutative operands are
 not looked at: a refactor that leaves the arithmetic alone leaves both alone.
 
   python tools/kernel_isa_diff.py BASE_TREE NEW_TREE [--out profiles/arith_policy_isa.txt]
+  python tools/kernel_isa_diff.py BASE_TREE NEW_TREE --sources k8_synth k13_fade k17_audio_synth k18_iq_audio
   (BASE_TREE: e.g. `git worktree add /tmp/parent HEAD~1`)
 """
 import argparse
@@ -107,14 +108,16 @@ def main():
     ap.add_argument("base")
     ap.add_argument("new")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--sources", nargs="+", default=list(SOURCES), metavar="NAME",
+                    help="files of csrc/kernels/ without .hip (default: %s)" % " ".join(SOURCES))
     a = ap.parse_args()
-    rep, gate_failed = [], False
+    rep, gate_failed, gated_seen = [], False, set()
     variants = (("plain", []), ("-DWSPR_LAB", ["-DWSPR_LAB"]))
-    jobs = [(tree, src, v) for v in range(2) for src in SOURCES for tree in (a.base, a.new)]
+    jobs = [(tree, src, v) for v in range(2) for src in a.sources for tree in (a.base, a.new)]
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(6, os.cpu_count() or 1)) as pool:
         asm = dict(zip(jobs, pool.map(lambda j: functions(assembly(j[0], j[1], variants[j[2]][1])), jobs)))
     for v, (variant, extra) in enumerate(variants):
-        for src in SOURCES:
+        for src in a.sources:
             base, new = asm[(a.base, src, v)], asm[(a.new, src, v)]
             base = {(RENAMED[k] if RENAMED.get(k) in new else k): f for k, f in base.items()}
             diffs = compare(base, new)
@@ -124,14 +127,20 @@ def main():
                 if g in new:
                     same = g in base and not any(name == g for name, _ in diffs)
                     gate_failed |= not same
+                    gated_seen.add(g)
                     rep.append("  gated %-30s %s  (vgpr %s, sgpr %s, lds %s, scratch %s, spills %s; %d instructions)" % (
                         g, "identical" if same else "DIFFERS", *[new[g]["meta"].get(k) for k in META], sum(new[g]["ops"].values())))
             for name, lines in diffs:
                 rep.append("  %s" % name)
+                if name in new and new[name]["meta"]:          # a kernel: its resources in the new tree, changed or not
+                    rep.append("      (new tree: vgpr %s, sgpr %s, lds %s, scratch %s, spills %s; %d instructions)" % (
+                        *[new[name]["meta"].get(k) for k in META], sum(new[name]["ops"].values())))
                 rep.extend("      " + l for l in lines)
     rep.append("")
-    rep.append("GATE: " + ("FAILED -- a gated kernel differs" if gate_failed else "passed -- the five gated kernels are identical "
-               "in opcode counts and resources in both builds"))
+    rep.append("GATE: " + ("FAILED -- a gated kernel differs" if gate_failed else
+                           "none of the gated kernels is in these sources" if not gated_seen else
+                           "passed -- the %s gated kernels are identical in opcode counts and resources in both builds"
+                           % {5: "five"}.get(len(gated_seen), len(gated_seen))))
     text = "\n".join(rep) + "\n"
     if a.out:
         with open(a.out, "w") as f:
