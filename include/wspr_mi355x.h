@@ -665,7 +665,10 @@ void subtract_signal2(float *id, float *qd, long np, float f0, int shift, float 
  * the spots it accepted;
  * then the lag pruning of the drifting candidates (their own coarse pass; [29]..[31] count drift-free candidates only),
  * summed like the counts: [41] drifting candidates pruned, [42] the exact single-lag evaluations they took, [43] drifting
- * candidates that fell back to the whole scan.
+ * candidates that fell back to the whole scan;
+ * then the spot-detail stage (wspr_set_spot_details(); both zero while it is off), summed like the counts: [44] the
+ * stage's device time, milliseconds (K19 with its transfers, taken without a host wait like the spread stage's), [45] the
+ * jobs it ran (one per spot the call's decode loops added).
  * Returns the number of values written (<= capacity). */
 int wspr_last_timings(double *ms, int capacity);
 /* Worker threads of the library's host pools alive in this process (the threads that call into the library are
@@ -809,7 +812,7 @@ int wspr_set_osd_depth(int depth);
  *     (B, rung) goes to the Fano search if the rung's mode-2 sync and the vector's own rms pass the gate of wsprd.c:758;
  *     the first success in (B, rung) order wins;
  *   - a success is a decode like any other -- spot, hash store, subtraction, de-duplication, loop exits -- reported with
- *     the rung's jitter and Fano's cycles; the spot record has no room for B (the lab trace has);
+ *     the rung's jitter and Fano's cycles; the spot record has no room for B (the record of wspr_set_spot_details() has);
  *   - with wspr_set_osd_depth() on as well this stage runs first, and the ordered-statistics stage sees only what it left
  *     undecoded (and uses the rung-0 vector of block size 1, as without this stage).
  * What to expect: on a stable channel the larger blocks raise the quality of the soft symbols of a weak signal without
@@ -963,6 +966,74 @@ typedef struct { int32_t index, score, second, v2; } wspr_list_match;   /* winne
 int wspr_set_message_list(const char *const *messages, int n, int zmin16);
 int wspr_message_list_entry(int index, char text[23], unsigned char decdata[11], unsigned char symbols[162]);
 int wspr_list_match_batch_device(const unsigned char *symbols, int n, wspr_list_match *out);
+/* Decode-quality figures and provenance per spot (kernel K19): which pass and which stage made a spot, and how well the
+ * soft-symbol vector that decoded agrees with the code word it decoded to -- what the extended spot tables of receiver
+ * farms carry besides sync, dt, drift, cycles and jitter, and what a farm filters false spots by before upload.  The
+ * reference reports none of this, so the definition is this library's own (rtlsdr-wsprd_amd/csrc/kernels/spot_quality.h;
+ * tests/helpers/spot_quality_check.c is its serial form), all of it integer.  THE FIGURES DESCRIBE THE VECTOR THAT DECODED,
+ * NOT THE CHANNEL.  A job is one vector of 162 soft symbols s[i] in transmission (interleaved) order, as
+ * wspr_fano_batch_device_wave() and wspr_osd_batch_device() take them, plus decdata[11] as fano() leaves it:
+ *   code word  c[i] in {0, 1}, i = 0 .. 161 in transmission order: the data bits of the code word that encode() +
+ *              interleave() make of the 50 message bits of decdata followed by 31 zero tail bits (whatever decdata holds
+ *              beyond bit 49 is not read).  The code word, not a re-encoding of the unpacked text: it exists for every decode
+ *              and needs no hash memory.
+ *   h, v, r    h[i] = (s[i] >= 128), v[i] = 2 s[i] - 255, r[i] = |v[i]|: the conventions of the ordered-statistics and of
+ *              the list stage.
+ *   nhard      the number of i with h[i] != c[i]: the hard errors.
+ *   dist       the sum of r[i] over those i.  For the winner of wspr_osd_batch_device() these two are its nhard and dist.
+ *   rsum       the sum of r[i] over all i.  rsum - 2 * dist is the score of that code word in wspr_list_match.
+ *   v2         the sum of v[i]^2: v2 of wspr_list_match.
+ *   metric     the sum over i of mettab[c[i]][s[i]] (int32), mettab = wspr_fano_metric_table(): the PATH METRIC.  For a vector
+ *              on which fano() succeeds it is what fano() returns in *metric, that unsigned word read as int32 (gamma is
+ *              signed inside the search; a decode through many wrong symbols ends below zero).
+ * wspr_spot_quality_batch_device(): K19 for n host vectors (n x 162 bytes) and their n x 11 bytes of decdata; out[i] = the
+ * figures of job i.  Returns 0; -1 with NOTHING WRITTEN without a usable device, for n < 0 or a missing array; n == 0 does
+ * nothing.  wspr_set_arithmetic() does not touch any of this.
+ *
+ * wspr_set_spot_details(): process-wide, 0 = off (the default), 1 = on; read once per decode call, on entry, like
+ * wspr_set_spread_estimate().  Returns the previous value; any other argument changes nothing and returns -2.  While it is
+ * on, every decode that ADDS A SPOT (not a duplicate, not beyond the 100 uniques, not a loop exit) gets one job, built on
+ * the vector that decoded it -- the rung's vector for a decode of the jitter ladder, the (block size, rung) vector for a
+ * decode of the block-detection stage, the FIRST (rung-0) vector for a list or an ordered-statistics decode -- read where it
+ * lies in device memory and queued behind the wave without a host wait.  Spots, hash memory, IQ and every other output are
+ * byte for byte what they are with the stage off; it works together with wspr_set_spread_estimate().
+ *
+ * wspr_last_spot_details(): the records of the calling thread's most recent decode call, in the layout of that call's
+ * `decodes` array, exactly as wspr_last_spreads() hands out its records -- entry s * max_results + i belongs to spot i of
+ * segment s (entry i for wspr_decode()); entries beyond n_results[s] are zero.  Returns the number of entries written
+ * (nseg * max_results; for wspr_decode(), *n_results), or -1 if the stage was off for that call, the capacity is too small,
+ * or the call was of a family that does not record them.  Recorded: wspr_decode(), wspr_decode_batch(),
+ * wspr_decode_batch_device(), wspr_decode_batch_hashed() (a segment decoded again reports its final round's records) and
+ * wspr_selftest().  NOT recorded, -1 afterwards: wspr_decode_batch_node(), wspr_decode_batch_node_device(),
+ * wspr_session_decode() and wspr_session_decode_many(), and a call that failed.  The stage is OFF by default, and bench.py
+ * measures the default. */
+typedef struct {
+    int32_t nhard, dist, rsum, v2, metric;
+} wspr_spot_quality;                /* 20 bytes */
+typedef struct {
+    int32_t nhard, dist, rsum, v2, metric;   /* the figures of the vector that decoded; all 0 unless valid */
+    uint8_t pass;                   /* the decode pass, 0-based */
+    uint8_t stage;                  /* WSPR_STAGE_*: which stage made the decode */
+    uint8_t block;                  /* block size of the demodulation: 1, or 2 / 3 for the block-detection stage */
+    uint8_t valid;                  /* 1 once the figures are filed */
+    int32_t cand;                   /* index in that pass's candidate list (strongest first) */
+    int32_t pad;
+} wspr_spot_detail;                 /* 32 bytes */
+#define WSPR_STAGE_LADDER 1         /* the reference's own decode: a rung of the jitter ladder */
+#define WSPR_STAGE_BLOCK2 2         /* block detection, block size 2 */
+#define WSPR_STAGE_BLOCK3 3         /* block detection, block size 3 */
+#define WSPR_STAGE_LIST   4         /* list decoding */
+#define WSPR_STAGE_OSD    5         /* ordered-statistics decoding */
+int wspr_spot_quality_batch_device(const unsigned char *symbols, const unsigned char *decdata, int n,
+                                   wspr_spot_quality *out);
+int wspr_set_spot_details(int on);
+int wspr_last_spot_details(wspr_spot_detail *details, int capacity);
+/* The "Spot : ..." line of wspr_format_spot() followed by six columns of the spot's record, each after one blank:
+ *   pass (%1d)  stage (%1d, WSPR_STAGE_*)  block (%1d)  nhard (%3d)  dist (%5d)  metric (%6d)
+ * e.g. "Spot : -21.04   0.11  14.097100  0  K1JT   FN20 20 0 1 1  23  1467   4012".  The project's own format: it does not
+ * claim to be the layout of any other program's spot file.  Returns what snprintf() returns: the length of the whole line,
+ * of which at most cap - 1 characters and the terminating NUL were written.  Host code: needs no device. */
+int wspr_format_spot_extended(const struct decoder_results *r, const wspr_spot_detail *d, char *out, size_t cap);
 /* Library / device description, e.g. for bench logs. */
 const char *wspr_mi355x_version(void);
 int wspr_device_ready(void);        /* 1 if a HIP device and the kernels are usable */

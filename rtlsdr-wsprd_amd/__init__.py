@@ -150,6 +150,14 @@ def _bind(path):
     L.wspr_set_spread_estimate.restype = C.c_int
     L.wspr_last_spreads.argtypes = [C.c_void_p, C.c_int]
     L.wspr_last_spreads.restype = C.c_int
+    L.wspr_spot_quality_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    L.wspr_spot_quality_batch_device.restype = C.c_int
+    L.wspr_set_spot_details.argtypes = [C.c_int]
+    L.wspr_set_spot_details.restype = C.c_int
+    L.wspr_last_spot_details.argtypes = [C.c_void_p, C.c_int]
+    L.wspr_last_spot_details.restype = C.c_int
+    L.wspr_format_spot_extended.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_size_t]
+    L.wspr_format_spot_extended.restype = C.c_int
     L.wspr_set_message_list.argtypes = [C.c_void_p, C.c_int, C.c_int]
     L.wspr_set_message_list.restype = C.c_int
     L.wspr_message_list_entry.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -364,6 +372,55 @@ def last_spreads(nseg, max_results, library=None):
     out = np.zeros((int(nseg), int(max_results)), SPREAD_DTYPE)
     n = (library or lib()).wspr_last_spreads(_ptr(out), int(out.size))
     return out if n == out.size else None
+
+
+# include/wspr_mi355x.h: wspr_spot_quality (the figures of one job of wspr_spot_quality_batch_device()) and
+# wspr_spot_detail (one record of wspr_last_spot_details(): the figures and the spot's provenance)
+SPOT_QUALITY_DTYPE = np.dtype([("nhard", "<i4"), ("dist", "<i4"), ("rsum", "<i4"), ("v2", "<i4"), ("metric", "<i4")])
+SPOT_DETAIL_DTYPE = np.dtype([("nhard", "<i4"), ("dist", "<i4"), ("rsum", "<i4"), ("v2", "<i4"), ("metric", "<i4"),
+                              ("pass", "u1"), ("stage", "u1"), ("block", "u1"), ("valid", "u1"), ("cand", "<i4"), ("pad", "<i4")])
+STAGE_LADDER, STAGE_BLOCK2, STAGE_BLOCK3, STAGE_LIST, STAGE_OSD = 1, 2, 3, 4, 5   # wspr_spot_detail.stage: WSPR_STAGE_*
+
+
+def set_spot_details(on, library=None):
+    """wspr_set_spot_details() of include/wspr_mi355x.h: 1 adds a record of decode-quality figures and provenance per spot
+    to every later decode call (read back with last_spot_details()), 0 switches it off (the default).  Returns the previous
+    value, or -2 (nothing changed) for any other argument.  The product and the lab library each keep their own setting."""
+    return (library or lib()).wspr_set_spot_details(int(on))
+
+
+def spot_quality_batch(symbols, decdata, library=None):
+    """wspr_spot_quality_batch_device(): the figures of n vectors of 162 soft symbols (uint8 [n, 162], transmission order)
+    against the code words of their decdata (uint8 [n, 11], as fano() leaves it).  Returns a SPOT_QUALITY_DTYPE array [n];
+    raises if the library refuses the call."""
+    sym = np.ascontiguousarray(symbols, dtype=np.uint8).reshape(-1, NSYM)
+    dec = np.ascontiguousarray(decdata, dtype=np.uint8).reshape(-1, 11)
+    if dec.shape[0] != sym.shape[0]:
+        raise ValueError("one decdata per vector")
+    out = np.zeros(sym.shape[0], SPOT_QUALITY_DTYPE)
+    rc = (library or lib()).wspr_spot_quality_batch_device(_ptr(sym), _ptr(dec), sym.shape[0], _ptr(out))
+    if rc != 0:
+        raise RuntimeError("wspr_spot_quality_batch_device failed (rc %d: bad arguments, or no usable HIP device)" % rc)
+    return out
+
+
+def last_spot_details(nseg, max_results, library=None):
+    """wspr_last_spot_details() for a call of nseg segments and max_results spots each: a SPOT_DETAIL_DTYPE array
+    [nseg, max_results] (entries beyond a segment's spots are zero), or None where the library answers -1 (stage off for
+    that call, or a call that does not record them)."""
+    out = np.zeros((int(nseg), int(max_results)), SPOT_DETAIL_DTYPE)
+    n = (library or lib()).wspr_last_spot_details(_ptr(out), int(out.size))
+    return out if n == out.size else None
+
+
+def format_spot_extended(result, detail, cap=160, library=None):
+    """wspr_format_spot_extended(): the "Spot : ..." line of a decoder_results followed by pass, stage, block, nhard, dist
+    and metric of its SPOT_DETAIL_DTYPE record.  Returns (text, length of the whole line); the text holds at most cap - 1
+    characters."""
+    rec = np.ascontiguousarray(np.asarray(detail, dtype=SPOT_DETAIL_DTYPE).reshape(1))
+    buf = C.create_string_buffer(max(1, int(cap)))
+    n = (library or lib()).wspr_format_spot_extended(C.byref(result), _ptr(rec), buf, int(cap))
+    return buf.value.decode("ascii", "replace"), n
 
 
 LIST_MAX = 65536                   # include/wspr_mi355x.h: WSPR_LIST_MAX
@@ -811,7 +868,8 @@ TIMING_NAMES = (
     "block_ms", "block_vectors", "block2_decodes", "block3_decodes",
     "spread_ms", "spread_jobs",
     "list_ms", "list_vectors", "list_spots",
-    "lag_drift_pruned", "lag_drift_exact_evals", "lag_drift_fallbacks")
+    "lag_drift_pruned", "lag_drift_exact_evals", "lag_drift_fallbacks",
+    "spot_detail_ms", "spot_detail_jobs")
 
 
 def last_timings():

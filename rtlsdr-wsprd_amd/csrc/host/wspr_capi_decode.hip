@@ -62,6 +62,16 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
         spread_rec = last.rec.data();
     }
     last.on = false;                                       // until this call has run to its end
+    // wspr_last_spot_details(): the same, for the records of wspr_set_spot_details()
+    wspr::LastDetails& last_det = wspr::last_details_of_thread();
+    wspr_spot_detail* detail_rec = nullptr;
+    if (settings.details > 0 && !trace && max_results > 0) {
+        const bool keep = revisit && last_det.on && last_det.nseg == nseg && last_det.max_results == max_results;
+        if (!keep) last_det.rec.assign((size_t)nseg * (size_t)max_results, wspr_spot_detail{});
+        last_det.nseg = nseg; last_det.max_results = max_results;
+        detail_rec = last_det.rec.data();
+    }
+    last_det.on = false;
     struct Share { int lo, hi; };
     std::vector<Share> share(nslots);
     for (int g = 0; g < nslots; ++g) share[g] = {(int)((long)nseg * g / nslots), (int)((long)nseg * (g + 1) / nslots)};
@@ -92,6 +102,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
             if (mine.empty()) return;
             reload(c, lo, mine);
             c.set_spread_out(spread_rec ? spread_rec + (size_t)lo * max_results : nullptr);
+            c.set_detail_out(detail_rec ? detail_rec + (size_t)lo * max_results : nullptr);
             c.decode_again(hi - lo, samples, options, decodes + (size_t)lo * max_results, max_results, n_results + lo, mine, hb, lo);
         });
     };
@@ -100,6 +111,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
             const int lo = share[g].lo, hi = share[g].hi;
             load(c, lo, hi - lo);
             c.set_spread_out(spread_rec ? spread_rec + (size_t)lo * max_results : nullptr);
+            c.set_detail_out(detail_rec ? detail_rec + (size_t)lo * max_results : nullptr);
             const int rc = c.decode_resident(hi - lo, samples, options, decodes + (size_t)lo * max_results, max_results, n_results + lo,
                                              [&c, &reload, lo](const std::vector<int>& segs) { reload(c, lo, segs); },
                                              trace ? trace + lo : nullptr, hb, lo);
@@ -126,6 +138,7 @@ int decode_split(int nseg, int samples, const decoder_options& options, decoder_
             c.store_host(idat + (size_t)lo * seg_stride, qdat + (size_t)lo * seg_stride, hi - lo, samples, seg_stride);
         });
     last.on = spread_rec != nullptr;
+    last_det.on = detail_rec != nullptr;
     return 0;
 }
 
@@ -393,6 +406,8 @@ int wspr_decode(float* idat, float* qdat, int samples, struct decoder_options op
     // wspr_last_spreads() follows the caller's array: entry i, n of them
     wspr::LastSpreads& last = wspr::last_spreads_of_thread();
     if (last.on && last.nseg == 1) { last.max_results = n < 0 ? 0 : n; last.rec.resize((size_t)last.max_results); }
+    wspr::LastDetails& last_det = wspr::last_details_of_thread();
+    if (last_det.on && last_det.nseg == 1) { last_det.max_results = n < 0 ? 0 : n; last_det.rec.resize((size_t)last_det.max_results); }
     return rc < 0 ? rc : 0;
 }
 

@@ -132,6 +132,13 @@ int wspr_format_spot(const struct decoder_results* r, char* out, size_t cap) {
                     r->call, r->loc, r->pwr);
 }
 
+// The same line followed by pass, stage, block, nhard, dist and metric of the spot's record (wspr_last_spot_details()).
+int wspr_format_spot_extended(const struct decoder_results* r, const wspr_spot_detail* d, char* out, size_t cap) {
+    return snprintf(out, cap, "Spot : %6.2f %6.2f %10.6f %2d %7s %6s %2s %1d %1d %1d %3d %5d %6d", r->snr, r->dt, r->freq,
+                    (int)r->drift, r->call, r->loc, r->pwr, (int)d->pass, (int)d->stage, (int)d->block, (int)d->nhard,
+                    (int)d->dist, (int)d->metric);
+}
+
 // ---- live-receiver output formats (formatting only, no network) ------
 // printSpots(), rtlsdr_wsprd.c:447-474: the daemon's stdout line with the UTC frame time.
 int wspr_format_spot_timestamped(const struct decoder_results* r, int year, int month, int day, int hour, int minute,

@@ -231,6 +231,7 @@ struct SegBook {                 // host bookkeeping of one segment across passe
     std::vector<int> dirty;      // hash slots written in the flat arena (single call with usehashtable)
     std::vector<decoder_results> spots;   // every unique spot, in decode order (the reference's 100 at most)
     std::vector<wspr_spread> spreads;     // wspr_set_spread_estimate(1): the figure of each, same order (else empty)
+    std::vector<wspr_spot_detail> details;   // wspr_set_spot_details(1): the record of each, same order (else empty)
 };
 
 struct Context::Impl {
@@ -270,6 +271,9 @@ struct Context::Impl {
     PinBuf h_sprjobs, h_sprout;      // ... the jobs on their way up, the results on their way down
     PinBuf h_noise;                  // K16: the records on their way down
     wspr_spread* spread_out = nullptr;   // where the current call's records go (the layout of its `decodes`), or null
+    DevBuf sq_where, sq_jobs, sq_out, sq_keep;   // K19: the coder output at each transmission position (built on first use), [offsets | decdata] of a batch, 5 words per job, vectors a stage hands on to the bookkeeping
+    PinBuf h_sqjobs, h_sqout;        // ... the jobs on their way up, the results on their way down
+    wspr_spot_detail* detail_out = nullptr;   // where the current call's records go (the layout of its `decodes`), or null
     PinBuf h_stage[2];
     PinBuf h_streamraw, h_streamstate, h_streamout;   // many receivers' callbacks at once (decimate_stream_many)
     hipEvent_t ev_stage[2] = {nullptr, nullptr};

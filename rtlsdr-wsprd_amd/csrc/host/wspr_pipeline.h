@@ -34,19 +34,21 @@ std::atomic<int>& front_end_cus();
 std::atomic<unsigned long long>& fano_handovers(int branch);
 #endif
 
-// The five process-wide settings a decode call honours: wspr_set_arithmetic() (0 exact, 1 contracted),
-// wspr_set_osd_depth() (-1 off, 0..3), wspr_set_block_detection() (1 off, 2, 3), wspr_set_spread_estimate() (0 off, 1 on)
-// and the list of wspr_set_message_list() (null: off; message_list_setting() in wspr_msglist.h).
+// The six process-wide settings a decode call honours: wspr_set_arithmetic() (0 exact, 1 contracted),
+// wspr_set_osd_depth() (-1 off, 0..3), wspr_set_block_detection() (1 off, 2, 3), wspr_set_spread_estimate() (0 off, 1 on),
+// wspr_set_spot_details() (0 off, 1 on) and the list of wspr_set_message_list() (null: off; message_list_setting() in
+// wspr_msglist.h).
 std::atomic<int>& arith_setting();
 std::atomic<int>& osd_depth_setting();
 std::atomic<int>& block_setting();
 std::atomic<int>& spread_setting();
+std::atomic<int>& details_setting();
 // A call reads them ONCE, on entry: the outermost entry point of the calling thread holds a CallScope, which takes the
 // snapshot, and everything the call does reads it through the call_*() accessors (outside a call they read the
 // process-wide value).  A thread the call starts for itself (slots, node workers) installs the caller's snapshot with
 // CallScope(settings).
 struct CallSettings {
-    int arith = 0, osd_depth = -1, maxblock = 1, spread = 0;
+    int arith = 0, osd_depth = -1, maxblock = 1, spread = 0, details = 0;
     std::shared_ptr<const MessageList> list;
     static CallSettings snapshot();
 };
@@ -56,6 +58,7 @@ inline int call_arith() { const CallSettings* s = call_settings_slot(); return s
 inline int call_osd_depth() { const CallSettings* s = call_settings_slot(); return s ? s->osd_depth : osd_depth_setting().load(); }
 inline int call_maxblock() { const CallSettings* s = call_settings_slot(); return s ? s->maxblock : block_setting().load(); }
 inline int call_spread() { const CallSettings* s = call_settings_slot(); return s ? s->spread : spread_setting().load(); }
+inline int call_details() { const CallSettings* s = call_settings_slot(); return s ? s->details : details_setting().load(); }
 inline std::shared_ptr<const MessageList> call_list() {
     const CallSettings* s = call_settings_slot();
     return s ? s->list : message_list_setting();
@@ -78,10 +81,17 @@ struct LastSpreads {
     std::vector<wspr_spread> rec;
 };
 LastSpreads& last_spreads_of_thread();
+// The same for wspr_last_spot_details(): the records of wspr_set_spot_details(), kept and handed out alike.
+struct LastDetails {
+    bool on = false;
+    int nseg = 0, max_results = 0;
+    std::vector<wspr_spot_detail> rec;
+};
+LastDetails& last_details_of_thread();
 // An entry point of a family that does not record them (node-level calls, receiver sessions): whatever batch calls it
-// made on the calling thread, wspr_last_spreads() answers -1 after it.
+// made on the calling thread, wspr_last_spreads() and wspr_last_spot_details() answer -1 after it.
 struct NoSpreadRecord {
-    ~NoSpreadRecord() { last_spreads_of_thread().on = false; }
+    ~NoSpreadRecord() { last_spreads_of_thread().on = false; last_details_of_thread().on = false; }
 };
 
 // The values of wspr_last_timings(), in the order include/wspr_mi355x.h documents (that order is ABI; the Python
@@ -99,6 +109,7 @@ enum TimingSlot : int {
     kTmSpreadMs, kTmSpreadJobs,
     kTmListMs, kTmListVectors, kTmListSpots,
     kTmLagDriftPruned, kTmLagDriftExactEvals, kTmLagDriftFallbacks,
+    kTmDetailMs, kTmDetailJobs,
     kTimingSlots
 };
 // A batch runs on several pipelines at once and each keeps its own values; wspr_last_timings() folds them.  The stage
@@ -106,7 +117,7 @@ enum TimingSlot : int {
 // from it on is SUMMED -- the counts, and the CPU times kTmCpuMs* as well (CPU time spent on different threads adds
 // up; the public header says "summed over the slots").
 constexpr int kTimingFirstSummed = kTmFanoCalls;
-static_assert(kTimingSlots == 44 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
+static_assert(kTimingSlots == 46 && kTimingFirstSummed == 7, "the layout of wspr_last_timings() is ABI");
 
 struct PendingFano {
     std::vector<int> seg;                 // owning segment of each attempt
@@ -228,6 +239,18 @@ public:
     const uint32_t* spread_enqueue(const SubJob* jobs, int n, int samples);
     const float* spread_twiddle_table();
     void set_spread_out(wspr_spread* out);
+    // K19 (k19_spot_quality.hip; the definition in kernels/spot_quality.h): the figures of n host vectors and their decdata;
+    // over vectors already in HBM, queued without a wait (n x 5 words in pinned memory once the stream has passed): jobs
+    // [first, first + count) of a group are the vectors at d_symbols + h_offsets[job] * 162 of that group's buffer -- a
+    // wave's decodes lie in up to three (rung 0, the ladder's block, vectors a stage handed on); decdata n x 11 on the
+    // host; where a decode call's records go
+    struct SpotQualityGroup { const unsigned char* d_symbols; int first, count; };
+    int spot_quality_batch(const unsigned char* symbols, const unsigned char* decdata, int n, wspr_spot_quality* out);
+    const int32_t* spot_quality_enqueue(const SpotQualityGroup* groups, int ngroups, const int* h_offsets,
+                                        const unsigned char* decdata, int n);
+    const unsigned char* spot_quality_where_table();
+    unsigned char* spot_quality_keep(size_t vectors);   // device room for vectors a stage hands on to the bookkeeping
+    void set_detail_out(wspr_spot_detail* out);
     int bench_decimate(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int iters, double* ms);
     int decimate_device(const void* d_raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ, int normalise,
                         int* h_nout, DecimState* d_states = nullptr);

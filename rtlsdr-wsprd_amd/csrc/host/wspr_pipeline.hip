@@ -14,6 +14,8 @@
 #include "wspr_context_impl.h"
 #include "wspr_fano_walk.h"
 
+#include <type_traits>
+
 namespace wspr {
 
 // ---------------------------------------------------------------- stages -----
@@ -114,6 +116,11 @@ namespace {
 // the stage whose decode an item carries (an item that is not decoded carries none)
 enum class Stage : unsigned char { None, Ladder, Block2, Block3, List, Osd, kCount };
 inline int block_of(Stage s) { return s == Stage::Block2 ? 2 : s == Stage::Block3 ? 3 : 1; }
+static_assert((int)Stage::Ladder == WSPR_STAGE_LADDER && (int)Stage::Block2 == WSPR_STAGE_BLOCK2 && (int)Stage::Block3 == WSPR_STAGE_BLOCK3 &&
+              (int)Stage::List == WSPR_STAGE_LIST && (int)Stage::Osd == WSPR_STAGE_OSD, "wspr_spot_detail::stage is Stage");
+// The three device buffers a wave's decoded vectors lie in: the rung-0 block (vector = the wave item), the ladder's 43-lag
+// block (vector = candidate x lag), and the vectors a stage whose own buffer does not last handed on (vector = the wave item)
+enum class VecSrc : unsigned char { Rung0, Ladder, Kept, kCount };
 
 struct WaveItem {
     int seg, cand;
@@ -125,8 +132,11 @@ struct WaveItem {
     int  jitter = 0;
     unsigned cycles = 0;                      // of the Fano search; 0 marks an ordered-statistics decode, 1 a list decode
     unsigned char decdata[11];
-    void decode_by(Stage st, int jit, unsigned cyc, const unsigned char* data11) {
-        decoded = true; stage = st; jitter = jit; cycles = cyc;
+    // where the vector that decoded it lies in HBM until the wave's bookkeeping: vector `voff` of the buffer `vsrc`
+    VecSrc vsrc = VecSrc::Rung0;
+    int voff = 0;
+    void decode_by(Stage st, int jit, unsigned cyc, const unsigned char* data11, VecSrc src, int off) {
+        decoded = true; stage = st; jitter = jit; cycles = cyc; vsrc = src; voff = off;
         memcpy(decdata, data11, 11);
     }
     void undecode() { decoded = false; stage = Stage::None; }
@@ -233,9 +243,13 @@ std::atomic<int>& spread_setting() {
     static std::atomic<int> v{0};
     return v;
 }
+std::atomic<int>& details_setting() {
+    static std::atomic<int> v{0};
+    return v;
+}
 CallSettings CallSettings::snapshot() {
     return CallSettings{arith_setting().load(), osd_depth_setting().load(), block_setting().load(), spread_setting().load(),
-                        message_list_setting()};
+                        details_setting().load(), message_list_setting()};
 }
 const CallSettings*& call_settings_slot() {
     thread_local const CallSettings* s = nullptr;
@@ -243,6 +257,10 @@ const CallSettings*& call_settings_slot() {
 }
 LastSpreads& last_spreads_of_thread() {
     thread_local LastSpreads l;
+    return l;
+}
+LastDetails& last_details_of_thread() {
+    thread_local LastDetails l;
     return l;
 }
 
@@ -368,7 +386,19 @@ struct Context::DecodeRun {
     const uint32_t* spr_words = nullptr;      // results of the jobs in flight (pinned), valid after a wait on the stream
     hipEvent_t spr_done = nullptr;
     int spr_def_top = -1;                     // c.n_def right after the stage's deferred event pair was recorded
-    ~DecodeRun() { if (spr_done) (void)hipEventDestroy(spr_done); }
+    // wspr_set_spot_details() of this call, handled like the spread stage: keep_books() leaves the wave's jobs here (one per
+    // decode that added a spot: where its vector lies, its decdata, the place of its record among the segment's spots),
+    // launch_details() queues K19 behind the wave, collect_details() files the figures once the stream has passed them.
+    const bool details_on = call_details() > 0;
+    struct DetailJob { int seg, spot; VecSrc src; int off; unsigned char decdata[11]; };
+    std::vector<DetailJob> det_jobs, det_flight;
+    const int32_t* det_words = nullptr;       // results of the jobs in flight (pinned), valid after a wait on the stream
+    hipEvent_t det_done = nullptr;
+    int det_def_top = -1;
+    ~DecodeRun() {
+        if (spr_done) (void)hipEventDestroy(spr_done);
+        if (det_done) (void)hipEventDestroy(det_done);
+    }
 
     // one Fano attempt on a soft-symbol vector in transmission order (wsprd.c:759-761)
     int fano_attempt(const unsigned char* tx_sym, unsigned* cycles, unsigned char* data11) const {
@@ -473,6 +503,8 @@ struct Context::DecodeRun {
     void subtract(const std::vector<SubJob>& jobs);
     void launch_spreads();
     void collect_spreads();
+    void launch_details();
+    void collect_details();
     void finish(const std::vector<int>& active0, int* n_results);
     void clear_hash(const std::vector<int>& segs);
 };
@@ -700,7 +732,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
         run_walk(fw, d_sym0, nullptr, nw);
         count_walk(fw, &FanoWalk::serial);                     // one rank: every attempt
         for (int i = 0; i < nw; ++i)
-            if (fw.at[i] >= 0) wave[i].decode_by(Stage::Ladder, 0, fw.res[fw.at[i]].cycles, fw.res[fw.at[i]].data);
+            if (fw.at[i] >= 0) wave[i].decode_by(Stage::Ladder, 0, fw.res[fw.at[i]].cycles, fw.res[fw.at[i]].data, VecSrc::Rung0, i);
         c.t_ms[kTmDeviceFanoTailMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f0).count();
         return;
     }
@@ -712,7 +744,7 @@ void Context::DecodeRun::refine_and_first_rung(std::vector<WaveItem>& wave) {
         if (!start_item(i)) return;
         WaveItem& w = wave[i];
         const int nd = fano_attempt(h_sym + (size_t)i * kNSymD, &w.cycles, w.decdata);
-        if (nd == 0) { w.decoded = true; w.stage = Stage::Ladder; }
+        if (nd == 0) { w.decoded = true; w.stage = Stage::Ladder; w.vsrc = VecSrc::Rung0; w.voff = i; }
         w.rung0_pending = (nd != 0) && fast;
         if (!w.rung0_pending) c.count_fano(nd, w.cycles);      // every attempt that ran to a final answer
     }, nw >= 256 ? 1 : 0);
@@ -775,7 +807,8 @@ void Context::DecodeRun::remaining_rungs(std::vector<WaveItem>& wave) {
             if (trace) { wtrace[again[a]].attempts = 1 + fw.walked(a); wtrace[again[a]].fano_calls += fw.calls[a]; }
             if (fw.at[a] < 0) continue;
             const FanoWalk::Result& r = fw.res[fw.at[a]];
-            wave[again[a]].decode_by(Stage::Ladder, c.jitter_ladder[fw.win[a] + 1], r.cycles, r.data);
+            wave[again[a]].decode_by(Stage::Ladder, c.jitter_ladder[fw.win[a] + 1], r.cycles, r.data, VecSrc::Ladder,
+                                     fw.att[fw.at[a]].off);
         }
         c.t_ms[c.dev_fano ? kTmDeviceFanoTailMs : kTmHostFanoMs] +=
             std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_f1).count();
@@ -797,6 +830,7 @@ void Context::DecodeRun::block_rescue(std::vector<WaveItem>& wave) {
     std::vector<BlockHyp> hyps;
     std::vector<unsigned char> sym;
     std::vector<float> rms, sy;
+    unsigned char* const d_keep = details_on ? ctx.spot_quality_keep(wave.size()) : nullptr;   // one place per wave item
     for (int lo = 0; lo < (int)todo.size(); lo += kChunk) {
         const int na = std::min(kChunk, (int)todo.size() - lo), nh = na * nr;
         hyps.resize(nh);
@@ -823,7 +857,13 @@ void Context::DecodeRun::block_rescue(std::vector<WaveItem>& wave) {
             if (fw.at[a] < 0) continue;
             const int b = fw.win[a] / nr, r = fw.win[a] % nr;
             const FanoWalk::Result& won = fw.res[fw.at[a]];
-            wave[todo[lo + a]].decode_by(b == 0 ? Stage::Block2 : Stage::Block3, c.jitter_ladder[r], won.cycles, won.data);
+            const int item = todo[lo + a];
+            wave[item].decode_by(b == 0 ? Stage::Block2 : Stage::Block3, c.jitter_ladder[r], won.cycles, won.data, VecSrc::Kept, item);
+            // the next chunk overwrites K10's vectors: the one that decoded is handed on to the bookkeeping, within this
+            // chunk's launch set (a copy on the stream, no wait)
+            if (details_on)
+                HIP_OK(hipMemcpyAsync(d_keep + (size_t)item * kNSymD, d_vec + (size_t)fw.att[fw.at[a]].off * kNSymD, kNSymD,
+                                      hipMemcpyDeviceToDevice, c.stream));
         }
     }
     c.t_ms[kTmBlockMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -844,7 +884,7 @@ void Context::DecodeRun::list_rescue(std::vector<WaveItem>& wave) {
     for (int k = 0; k < na; ++k) {
         const wspr_list_match& r = res[k];
         if (r.index < 0 || r.index >= list->n || !listmatch::gate(r.score, r.v2, list->zmin16)) continue;
-        wave[att[k]].decode_by(Stage::List, 0, 1, list->decdata.data() + (size_t)r.index * 11);
+        wave[att[k]].decode_by(Stage::List, 0, 1, list->decdata.data() + (size_t)r.index * 11, VecSrc::Rung0, att[k]);
     }
     c.t_ms[kTmListMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c.t_ms[kTmListVectors] += (double)na;
@@ -863,7 +903,7 @@ void Context::DecodeRun::osd_rescue(std::vector<WaveItem>& wave) {
     std::vector<unsigned char> dat((size_t)na * 11);
     std::vector<unsigned> dist(na), nhard(na), order(na);
     ctx.osd_resident(d_sym0, att.data(), na, osd_depth, dat.data(), dist.data(), nhard.data(), order.data());
-    for (int k = 0; k < na; ++k) wave[att[k]].decode_by(Stage::Osd, 0, 0, dat.data() + (size_t)k * 11);
+    for (int k = 0; k < na; ++k) wave[att[k]].decode_by(Stage::Osd, 0, 0, dat.data() + (size_t)k * 11, VecSrc::Rung0, att[k]);
     c.t_ms[kTmOsdMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c.t_ms[kTmOsdVectors] += (double)na;
 }
@@ -883,6 +923,7 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
     std::vector<char> has_job(nw, 0);
     std::vector<SubJob> spr_of(spread_on ? nw : 0);
     std::vector<int> spr_spot(spread_on ? nw : 0, -1);
+    std::vector<DetailJob> det_of(details_on ? nw : 0, DetailJob{-1, -1, VecSrc::Rung0, 0, {0}});
     c.pool->run(ngroups, [&](int g) {
       const int sg = wave[group_start[g]].seg;
       bool cut = false;
@@ -978,6 +1019,15 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
             copy_text(o->loc, sizeof o->loc, loc);
             copy_text(o->pwr, sizeof o->pwr, pwr);
         }
+        if (details_on) {
+            // provenance now, the figures when K19 has run on the vector that decoded this item
+            wspr_spot_detail dt{};
+            dt.pass = (uint8_t)ipass; dt.stage = (uint8_t)w.stage; dt.block = (uint8_t)block_of(w.stage); dt.cand = w.cand;
+            DetailJob& dj = det_of[i];
+            dj.seg = s; dj.spot = (int)bk.details.size(); dj.src = w.vsrc; dj.off = w.voff;
+            memcpy(dj.decdata, w.decdata, 11);
+            bk.details.push_back(dt);
+        }
         if (spread_on) {
             // the figure is taken with the decode's own parameters and the symbols its message re-encodes to -- against a
             // table that takes no stores and logs no look-ups: the hash memory is what it is without the stage
@@ -1011,6 +1061,10 @@ std::vector<SubJob> Context::DecodeRun::keep_books(std::vector<WaveItem>& wave) 
         spr_jobs.clear(); spr_slots.clear();
         for (int i = 0; i < nw; ++i)
             if (spr_spot[i] >= 0) { spr_jobs.push_back(spr_of[i]); spr_slots.push_back(SpreadSlot{wave[i].seg, spr_spot[i]}); }
+    }
+    if (details_on) {
+        det_jobs.clear();
+        for (int i = 0; i < nw; ++i) if (det_of[i].spot >= 0) det_jobs.push_back(det_of[i]);
     }
     c.t_ms[kTmHostBookkeepingMs] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_b0).count();
     return jobs;
@@ -1077,6 +1131,55 @@ void Context::DecodeRun::collect_spreads() {
     spr_flight.clear();
 }
 
+// GPU: the decode-quality figures of every decode of this wave that added a spot (K19), queued right behind the wave: the
+// vectors are read where the wave's kernels left them, before the next wave's launches reuse those buffers (same stream).
+// No host wait: the results come down behind the kernel and are filed by collect_details().
+void Context::DecodeRun::launch_details() {
+    if (!details_on) return;
+    collect_details();                                     // one batch in flight: its pinned words are about to be reused
+    if (det_jobs.empty()) return;
+    // jobs of one buffer side by side: one launch each
+    std::stable_sort(det_jobs.begin(), det_jobs.end(), [](const DetailJob& a, const DetailJob& b) { return a.src < b.src; });
+    const int nj = (int)det_jobs.size();
+    const unsigned char* base[(int)VecSrc::kCount] = {d_sym0, d_sym, c.sq_keep.as<unsigned char>()};
+    std::vector<Context::SpotQualityGroup> groups;
+    std::vector<int> off(nj);
+    std::vector<unsigned char> dec((size_t)nj * 11);
+    for (int i = 0; i < nj; ++i) {
+        const DetailJob& j = det_jobs[i];
+        off[i] = j.off;
+        memcpy(dec.data() + (size_t)i * 11, j.decdata, 11);
+        if (groups.empty() || groups.back().d_symbols != base[(int)j.src]) groups.push_back({base[(int)j.src], i, 0});
+        groups.back().count++;
+    }
+    const int slot_ev = c.n_def < Impl::kDeferred ? c.n_def : -1;
+    if (slot_ev >= 0) HIP_OK(hipEventRecord(c.ev_def[slot_ev][0], c.stream));
+    det_words = ctx.spot_quality_enqueue(groups.data(), (int)groups.size(), off.data(), dec.data(), nj);
+    if (slot_ev >= 0) {
+        HIP_OK(hipEventRecord(c.ev_def[slot_ev][1], c.stream));
+        c.def_acc[slot_ev] = &c.t_ms[kTmDetailMs];
+        c.n_def = slot_ev + 1;
+    }
+    det_def_top = slot_ev >= 0 ? c.n_def : -1;
+    if (!det_done) HIP_OK(hipEventCreateWithFlags(&det_done, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(det_done, c.stream));
+    det_flight.swap(det_jobs);
+    c.t_ms[kTmDetailJobs] += (double)nj;
+    det_jobs.clear();
+}
+
+void Context::DecodeRun::collect_details() {
+    if (det_flight.empty()) return;
+    host_wait(det_done);                                   // usually long passed: a wave's own waits lie in between
+    if (c.n_def == det_def_top) c.resolve_deferred();      // nothing was queued behind the stage's own event pair: all have passed
+    for (size_t i = 0; i < det_flight.size(); ++i) {
+        wspr_spot_detail& dt = book[det_flight[i].seg].details[(size_t)det_flight[i].spot];
+        memcpy(&dt, det_words + 5 * i, 20);                // nhard, dist, rsum, v2, metric; the provenance is keep_books()'s
+        dt.valid = 1;
+    }
+    det_flight.clear();
+}
+
 // results strongest first (wsprd.c:827; stable like glibc's merge sort) -- ALL unique spots of the segment
 // are ranked, then the strongest max_results are handed out (a caller with a short array loses the weakest
 // spots, never a strong one that happened to decode late); hash slots written by the batch are cleared again
@@ -1087,25 +1190,32 @@ void Context::DecodeRun::clear_hash(const std::vector<int>& segs) {
 
 void Context::DecodeRun::finish(const std::vector<int>& active0, int* n_results) {
     if (spread_on) collect_spreads();
+    if (details_on) collect_details();
     for (int s : active0) {
         SegBook& bk = book[s];
-        if (spread_on) {
-            // the same stable permutation and the same cut for the spots and their figures
+        if (spread_on || details_on) {
+            // the same stable permutation and the same cut for the spots and their records
             const int m = (int)bk.spots.size();
             std::vector<int> order(m);
             for (int i = 0; i < m; ++i) order[i] = i;
             std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return bk.spots[a].snr > bk.spots[b].snr; });
             std::vector<decoder_results> sp(m);
-            std::vector<wspr_spread> fig(m);
-            for (int i = 0; i < m; ++i) { sp[i] = bk.spots[order[i]]; fig[i] = bk.spreads[order[i]]; }
-            bk.spots.swap(sp); bk.spreads.swap(fig);
+            for (int i = 0; i < m; ++i) sp[i] = bk.spots[order[i]];
+            bk.spots.swap(sp);
             const int n = std::min(m, max_results);
             if (n > 0) memcpy(out + (size_t)s * max_results, bk.spots.data(), (size_t)n * sizeof(decoder_results));
-            if (c.spread_out) {
-                wspr_spread* so = c.spread_out + (size_t)s * max_results;
-                if (n > 0) memcpy(so, bk.spreads.data(), (size_t)n * sizeof(wspr_spread));
-                if (max_results > n) memset(so + n, 0, (size_t)(max_results - n) * sizeof(wspr_spread));
-            }
+            // one kind of record in the order of the spots, handed out where the call keeps that kind (or nowhere)
+            auto hand_out = [&](auto& rec, auto* where) {
+                typename std::remove_reference<decltype(rec)>::type sorted(m);
+                for (int i = 0; i < m; ++i) sorted[i] = rec[order[i]];
+                rec.swap(sorted);
+                if (!where) return;
+                auto* to = where + (size_t)s * max_results;
+                if (n > 0) memcpy(to, rec.data(), (size_t)n * sizeof(*to));
+                if (max_results > n) memset(to + n, 0, (size_t)(max_results - n) * sizeof(*to));
+            };
+            if (spread_on) hand_out(bk.spreads, c.spread_out);
+            if (details_on) hand_out(bk.details, c.detail_out);
             n_results[s] = n;
             continue;
         }
@@ -1127,7 +1237,7 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
                          const FanoMemo* memo, wspr_trace* trace, HashBatch* hb, int hb_off) {
     for (int s : active0) n_results[s] = 0;
     DecodeRun run(*this, nseg, samples, opt, out, max_results, fast, pend);
-    for (int s : active0) { SegBook& b = run.book[s]; b.uniques = 0; b.dirty.clear(); b.hash.entries.clear(); b.spots.clear(); b.spreads.clear(); }
+    for (int s : active0) { SegBook& b = run.book[s]; b.uniques = 0; b.dirty.clear(); b.hash.entries.clear(); b.spots.clear(); b.spreads.clear(); b.details.clear(); }
     run.memo = memo;
     run.trace = trace;
     run.hb = hb;
@@ -1165,6 +1275,7 @@ int Context::decode_core(int nseg, int samples, const decoder_options& opt, deco
             if (run.osd_depth >= 0) { CpuSpan sp(&d->t_ms[kTmCpuMsLadder]); run.osd_rescue(wave); }
             std::vector<SubJob> jobs;
             { CpuSpan sp(&d->t_ms[kTmCpuMsBooks]); jobs = run.keep_books(wave); }
+            if (run.details_on) { CpuSpan sp(&d->t_ms[kTmCpuMsSubtract]); run.launch_details(); }
             if (run.spread_on) { CpuSpan sp(&d->t_ms[kTmCpuMsSubtract]); run.launch_spreads(); }
             { CpuSpan sp(&d->t_ms[kTmCpuMsSubtract]); run.subtract(jobs); }
         }
@@ -1572,6 +1683,69 @@ int Context::list_batch(const unsigned char* symbols, int n, const MessageList& 
     const unsigned char* dsym = stage_vectors(*d, symbols, n, off);
     return list_resident(dsym, off.data(), n, list, out);
 }
+
+// K19 (the definition in kernels/spot_quality.h).  where[i] = the coder output sent at transmission position i, taken from
+// the message layer's own interleaver; built on first use: a process that never asks for the figures allocates nothing.
+const unsigned char* Context::spot_quality_where_table() {
+    Impl& c = *d;
+    if (!c.sq_where.p) {
+        static const std::vector<unsigned char> host = [] {
+            std::vector<unsigned char> t(kNSymD);
+            for (int k = 0; k < kNSymD; ++k) t[k] = (unsigned char)k;
+            interleave162(t.data());
+            return t;
+        }();
+        void* p = c.sq_where.need(host.size());
+        HIP_OK(hipMemcpy(p, host.data(), host.size(), hipMemcpyHostToDevice));
+    }
+    return c.sq_where.as<unsigned char>();
+}
+
+unsigned char* Context::spot_quality_keep(size_t vectors) {
+    return static_cast<unsigned char*>(d->sq_keep.need(std::max<size_t>(1, vectors) * kNSymD));
+}
+
+// Queues K19 over n jobs: [offsets | decdata] -> pinned staging -> device in one copy, one launch per group, the 20-byte
+// results back into pinned memory in one copy.  Nothing waits; the returned pointer holds n x 5 words once the stream has
+// passed this point.
+const int32_t* Context::spot_quality_enqueue(const SpotQualityGroup* groups, int ngroups, const int* h_offsets,
+                                             const unsigned char* decdata, int n) {
+    static_assert(sizeof(SpotQuality) == 20 && sizeof(wspr_spot_quality) == 20, "public and device result layouts differ");
+    Impl& c = *d;
+    const unsigned char* where = spot_quality_where_table();
+    const size_t o_dec = (size_t)n * 4, blk = o_dec + (size_t)n * 11;
+    char* hj = static_cast<char*>(c.h_sqjobs.need(blk));
+    memcpy(hj, h_offsets, o_dec);
+    memcpy(hj + o_dec, decdata, (size_t)n * 11);
+    char* dj = static_cast<char*>(c.sq_jobs.need(blk));
+    SpotQuality* dout = static_cast<SpotQuality*>(c.sq_out.need((size_t)n * sizeof(SpotQuality)));
+    int32_t* hout = static_cast<int32_t*>(c.h_sqout.need((size_t)n * sizeof(SpotQuality)));
+    upload(dj, hj, blk, c.stream);
+    for (int g = 0; g < ngroups; ++g) {
+        const SpotQualityGroup& q = groups[g];
+        if (q.count <= 0 || q.first < 0 || q.first + q.count > n) continue;
+        launch_spot_quality(q.d_symbols, reinterpret_cast<const int*>(dj) + q.first,
+                            reinterpret_cast<const unsigned char*>(dj + o_dec) + (size_t)q.first * 11, q.count,
+                            c.t_metric0.as<short>(), where, dout + q.first, c.stream);
+    }
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(hout, dout, (size_t)n * sizeof(SpotQuality), hipMemcpyDeviceToHost, c.stream));
+    return hout;
+}
+
+// K19 over n host vectors (wspr_spot_quality_batch_device)
+int Context::spot_quality_batch(const unsigned char* symbols, const unsigned char* decdata, int n, wspr_spot_quality* out) {
+    if (n <= 0) return 0;
+    std::vector<int> off;
+    const unsigned char* dsym = stage_vectors(*d, symbols, n, off);
+    const SpotQualityGroup all{dsym, 0, n};
+    const int32_t* words = spot_quality_enqueue(&all, 1, off.data(), decdata, n);
+    sync();
+    memcpy(out, words, (size_t)n * sizeof(wspr_spot_quality));
+    return 0;
+}
+
+void Context::set_detail_out(wspr_spot_detail* out) { d->detail_out = out; }
 
 // K9 over n host vectors (wspr_osd_batch_device)
 int Context::osd_batch(const unsigned char* symbols, int n, int depth, unsigned char* data, unsigned* dist,

@@ -1,4 +1,4 @@
-// What can be wrong with a stage call (K8/K13, K12, K15, K16, K17, K18), each condition stated once.  Plain C++ without
+// What can be wrong with a stage call (K8/K13, K12, K15, K16, K17, K18, K19), each condition stated once.  Plain C++ without
 // HIP: pointers are looked at as addresses and never dereferenced -- the transmissions, their channels and the noise
 // windows are host memory and are read.  tests/helpers/stage_args_check.cpp runs a table of calls through this header on
 // a CPU.
@@ -230,6 +230,13 @@ inline int iq_audio_batch(const char* where, const void* d_i, const void* d_q, i
 inline int iq_audio_host(const char* where, const void* I, const void* Q, int samples, float gain, const void* pcm) {
     if (const int bad = iq_audio_args_bad(where, 1, samples, gain)) return bad;
     return ((!I || !Q || !pcm) && samples) ? refuse(where, "no row or no output record") : 0;
+}
+// wspr_spot_quality_batch_device() (K19): n host vectors of 162 bytes, n x 11 bytes of decdata, n records out
+inline int spot_quality_batch(const char* where, const void* symbols, const void* decdata, int n, const void* out) {
+    if (n < 0) return refuse(where, "negative count");
+    if (n > 0 && (!symbols || !decdata)) return refuse(where, "no vectors or no decdata");
+    if (n > 0 && !out) return refuse(where, "no output records");
+    return 0;
 }
 
 }  // namespace args

@@ -309,5 +309,14 @@ struct ListMatch {
 };
 void launch_list_match(const unsigned char* symbols, const int* offsets, int n, const int* table, const int* bias, int m,
                        ListMatch* out, hipStream_t st);
+// K19, the decode-quality figures of a spot (k19_spot_quality.hip; the definition in spot_quality.h): job i = the 162 soft
+// symbols at symbols + offsets[i] * 162 (transmission order) against the code word of decdata + i * 11.  metric0: row 0 of
+// the Fano metric table as 256 shorts (K6w's table); where: 162 bytes, the coder output sent at each transmission position.
+// SpotQuality is wspr_spot_quality of the public header: one per job.
+struct SpotQuality {
+    int32_t nhard, dist, rsum, v2, metric;
+};
+void launch_spot_quality(const unsigned char* symbols, const int* offsets, const unsigned char* decdata, int n,
+                         const short* metric0, const unsigned char* where, SpotQuality* out, hipStream_t st);
 
 }  // namespace wspr
