@@ -23,6 +23,10 @@
  *   -W                   (before -r or -t) switches the Doppler-spread stage on (wspr_set_spread_estimate()) and appends
  *                        " w50 <Hz>" to every spot line ("w50 -" where the figure is not valid).  Without it the output is
  *                        what it always was.  The receiver sessions (-i) keep no such records: -W changes nothing there.
+ *   --waterfall FILE.png (before -r or -t) writes the picture of the slot that is decoded -- the first file of -r, or the
+ *                        self-test's -- as it was BEFORE the decode (which leaves its residual in the rows): the waterfall
+ *                        of wspr_waterfall() with the default parameters through the colour ramp.  A message on stderr,
+ *                        stdout unchanged; a picture that cannot be made or written is exit status 4.
  *
  * Build: make -C examples      (gcc, links ../rtlsdr-wsprd_amd/libwspr_mi355x.so with an rpath)
  */
@@ -44,7 +48,7 @@ static const char kHeader[] = "        SNR      DT        Freq Dr    Call    Loc
 
 static void usage(const char *argv0) {
     fprintf(stderr,
-            "use: %s [-f dial_hz] [-c call] [-l locator] [-H] [-Q] [-S] [-W] (-r FILE [FILE ...] | -t | -i RAWFILE|- [-i RAWFILE ...] [-T utc_seconds])\n",
+            "use: %s [-f dial_hz] [-c call] [-l locator] [-H] [-Q] [-S] [-W] [--waterfall FILE.png] (-r FILE [FILE ...] | -t | -i RAWFILE|- [-i RAWFILE ...] [-T utc_seconds])\n",
             argv0);
 }
 
@@ -56,6 +60,27 @@ static void spread_suffix(const wspr_spread *r, char *out, size_t cap) {
     if (!g_spread) return;
     if (r && r->valid) snprintf(out, cap, " w50 %.3f", r->w50);
     else snprintf(out, cap, " w50 -");
+}
+
+static const char *g_waterfall = NULL;     /* --waterfall */
+
+/* the picture of one row of `samples` samples into g_waterfall, if asked for: 0, or 4 */
+static int write_waterfall(const float *I, const float *Q, int samples) {
+    if (!g_waterfall) return 0;
+    int nrows = 0, ncols = 0;
+    uint8_t rgb[768];
+    wspr_waterfall_info info;
+    if (wspr_waterfall_shape(samples, NULL, &nrows, &ncols) != 0 || nrows < 1) { fprintf(stderr, "no waterfall of %d samples\n", samples); return 4; }
+    uint8_t *img = malloc((size_t)nrows * (size_t)ncols);
+    if (!img) { fprintf(stderr, "out of memory\n"); return 4; }
+    int rc = wspr_waterfall(I, Q, samples, NULL, img, &info) == 0 ? 0 : 4;
+    if (rc == 0) {
+        wspr_waterfall_palette(1, rgb);
+        if (wspr_write_png_file(g_waterfall, img, ncols, nrows, rgb) != 0) { fprintf(stderr, "cannot write %s\n", g_waterfall); rc = 4; }
+        else fprintf(stderr, "%s: %d x %d, 0 dB = %g%s\n", g_waterfall, ncols, nrows, info.ref, (info.flags & WSPR_WF_NO_REF) ? " (no floor)" : "");
+    }
+    free(img);
+    return rc;
 }
 
 static int has_suffix(const char *name, const char *suffix) {
@@ -84,6 +109,7 @@ static int playback(int nfiles, char **files, struct decoder_options opt) {
             rc = 2;
         }
     }
+    if (rc == 0 && nread[0] > 0) rc = write_waterfall(I, Q, nread[0]);
     if (rc == 0) {
         /* a single file is the reference's call as it stands (its `samples` argument is what was read); several files
          * are one batch of whole records -- the readers zero-fill short files -- decoded together */
@@ -146,6 +172,7 @@ static int self_test(struct decoder_options opt) {
         }
     }
     wspr_write_iq_file("selftest.iq", I, Q);
+    if (write_waterfall(I, Q, SLOT_SAMPLES) != 0) return 4;
     struct decoder_results spots[MAX_SPOTS];
     int n = 0;
     memset(spots, 0, sizeof spots);
@@ -265,6 +292,11 @@ int main(int argc, char **argv) {
     int first_file = 0;
     for (int a = 1; a < argc; ++a) {
         const char *o = argv[a];
+        if (strcmp(o, "--waterfall") == 0) {
+            if (a + 1 >= argc) { usage(argv[0]); return 2; }
+            g_waterfall = argv[++a];
+            continue;
+        }
         if (o[0] != '-' || o[1] == '\0' || o[2] != '\0') { usage(argv[0]); return 2; }
         const int wants_value = strchr("fclirT", o[1]) != NULL;
         if (wants_value && a + 1 >= argc) { usage(argv[0]); return 2; }

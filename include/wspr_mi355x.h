@@ -547,6 +547,86 @@ int wspr_iq_to_audio_batch_device(const void *d_idat, const void *d_qdat, int ns
  * int, may be NULL. */
 int wspr_iq_to_audio(const float *I, const float *Q, int samples, float gain, int16_t *pcm /* 32*samples */, int *n_clipped);
 
+/* ---- waterfall: dB-quantised spectrogram images (K20) --------------------------------------------------------------
+ * What was on the band during a slot, as a picture: one byte per (time, frequency) cell, made on the device from the
+ * resident 375 Hz rows -- 105 KB to fetch by default (hop 128; 52 KB at hop 256) where the row is 360 KB -- and two file writers to look at it.  The reference
+ * computes no such picture, so the definition is this library's own (rtlsdr-wsprd_amd/csrc/kernels/waterfall.h over
+ * noise.h; tests/helpers/waterfall_check.c is its serial form, and the kernel equals it byte for byte).  It is K16's frame
+ * transform with the frames kept instead of averaged: window, twiddles, butterfly, bin order and W2 are those of the band
+ * noise figures above.  The parameters are an argument of the calls, not state:
+ *   hop       128 or 256 samples between frames of 512 (128 is the reference's own frame step, two rows per symbol)
+ *   tavg      1 .. 16 frames averaged into one image row
+ *   j0, j1    signed bins, -256 <= j0 <= j1 <= 255; bin j lies at j*375/512 Hz; ncols = j1 - j0 + 1
+ *   ref_mode  WSPR_WF_REF_ABSOLUTE: `ref`, finite and > 0, in K16's units (linear power per complex sample);
+ *             WSPR_WF_REF_FLOOR: the row's own K16 fft_p30
+ *   db_min    level 0 is "below db_min + db_step"; -60 .. 60        db_step  dB per level, 0.05 .. 4
+ * wspr_waterfall_default_params(): hop 128, tavg 1, bins -150 .. 150 (+-109.9 Hz, the search band, 301 columns), floor
+ * mode, db_min -10, db_step 0.25: the levels span -10 .. +53.75 dB over the floor.
+ * For one row of np samples (0 .. 45 000):
+ *   frames    nframes = np >= 512 ? (np - 512)/hop + 1 : 0; frame f holds the samples hop*f .. hop*f + 511.  nrows = nframes /
+ *             tavg; image row r is formed from the frames r*tavg .. r*tavg + tavg - 1; a trailing incomplete group is dropped.
+ *             Row 0 is the earliest; column c is bin j0 + c, so +f is to the right.  348 (hop 128) or 174 rows for a full row.
+ *   power     P_f[j] exactly K16's (float products with the Hann window, nine stages, re*re + im*im separately rounded, no
+ *             fused multiply-add).  M = the double sum of (double)P_f[j] over the row's frames in rising f from 0.0;
+ *             m = (float)(M / (double)tavg / W2): the units of K16's a[j].
+ *   reference absolute mode: `ref`.  Floor mode: the fft_p30 that wspr_noise_batch_device() returns for the same row and
+ *             `samples`, bit for bit (K16's own hop of 256 whatever hop is here; the windows play no part).  There is no
+ *             usable floor when K16's record lacks WSPR_NOISE_FFT_USED, carries WSPR_NOISE_NONFINITE or has fft_p30 == 0:
+ *             then info.ref = 0, flags gets WSPR_WF_NO_REF (and WSPR_WF_NONFINITE if K16 reported it) and every pixel is 0.
+ *   guard     (when a reference exists) if any sample of hop*(r*tavg) .. hop*(r*tavg + tavg - 1) + 511, the samples image row
+ *             r is formed from, has exponent bits 0xff on either rail, every pixel of row r is 255 and WSPR_WF_NONFINITE is
+ *             set: a white stripe where the capture is garbage.  Samples that no complete row uses are not looked at.
+ *   level     r = (double)m / (double)ref;  T[i] = pow(10.0, ((double)db_min + (double)i*(double)db_step)/10.0), i = 1 .. 255,
+ *             from the host libm in double.  The pixel is the number of i with r >= T[i]: a NaN r gives 0, +Inf gives 255.
+ *             (No logarithm runs on the device: it searches the table.)
+ *   info      the ref used, nframes, nrows, flags; WSPR_WF_WRITTEN iff nrows > 0.
+ * wspr_set_arithmetic() does not touch this stage, and no decode call runs it.
+ *
+ * wspr_waterfall_shape(): nrows and ncols (either may be NULL) of a row of `samples` samples under p.  Returns 0; -1 for
+ * samples < 0 or parameters out of range, -2 for samples > 45000.  Needs no device.
+ * wspr_waterfall_batch_device(): input rows as for wspr_noise_batch_device().  Image s lies at (uint8_t*)d_img +
+ * s*img_stride and pixel (r, c) at + r*ncols + c; d_img is 16-byte aligned device memory, img_stride a multiple of 16 and >=
+ * nrows*ncols.  Bytes [0, nrows*ncols) of each image are written, everything behind them is left alone; info[0 .. nseg) is
+ * HOST memory.  Returns 0; -1 with a line on stderr and NOTHING WRITTEN (info included) for: no device, negative counts,
+ * misalignment, a stride too small or no multiple of its unit, hop other than 128 / 256, tavg outside 1 .. 16, bins outside
+ * -256 <= j0 <= j1 <= 255, an unknown ref_mode, absolute mode with a ref that is not finite and > 0, db_min or db_step
+ * non-finite or out of range, info == NULL; -2 for samples > 45000.  nseg == 0 does nothing; samples < 512 writes no pixel
+ * and gives info records with nrows 0.  Stream contract and lane turn as wspr_audio_batch_device(); the scratch (16 bytes
+ * per segment, 32 more in floor mode, two tables of 4 KB and 2 KB) belongs to the lane's context and is returned by
+ * wspr_release_buffers().
+ * wspr_waterfall(): one row from host memory (any alignment) into an image of nrows*ncols bytes in host memory: row 0 of the
+ * batch call.
+ *
+ * wspr_waterfall_palette(): 256 RGB triples for the levels.  which = 0: grey, (v, v, v).  which = 1 (any other value is taken
+ * as 1): a piecewise-linear integer ramp black - blue - cyan - yellow - red - white: with k = min(v / 51, 4) and t = v - 51*k
+ * (integer division), (R, G, B) = k = 0: (0, 0, 5t);  k = 1: (0, 5t, 255);  k = 2: (5t, 255, 255 - 5t);  k = 3: (255, 255 - 5t, 0);
+ * k = 4: (255, 5t, 5t).
+ * wspr_write_pgm_file(): binary P5, "P5\n<width> <height>\n255\n" and the bytes.  wspr_write_png_file(): 8 bits per sample,
+ * colour type 0 (grey), or colour type 3 with a PLTE of the 256 entries when rgb768 is given; one IDAT chunk holding one zlib
+ * stream of stored deflate blocks, filter 0 on every scan line; no compression and no library.  Both take width, height >= 1
+ * (width * height + height below 2^31), image row 0 on top, and return 0, or -1 if the arguments are unusable or the file
+ * cannot be written.  Host code: they need no device. */
+#define WSPR_WF_REF_ABSOLUTE 0
+#define WSPR_WF_REF_FLOOR    1
+#define WSPR_WF_WRITTEN   1   /* nrows > 0 and pixels were written */
+#define WSPR_WF_NO_REF    2   /* floor mode and no usable floor: every pixel is 0 */
+#define WSPR_WF_NONFINITE 8   /* some image row was guarded */
+typedef struct wspr_waterfall_params {      /* 32 bytes */
+    int32_t hop, tavg, j0, j1, ref_mode;
+    float   ref, db_min, db_step;
+} wspr_waterfall_params;
+typedef struct wspr_waterfall_info { float ref; int32_t nframes, nrows, flags; } wspr_waterfall_info;   /* 16 bytes */
+void wspr_waterfall_default_params(wspr_waterfall_params *p);
+int wspr_waterfall_shape(int samples, const wspr_waterfall_params *p /* NULL = default */, int *nrows, int *ncols);
+int wspr_waterfall_batch_device(const void *d_idat, const void *d_qdat, int nseg, int samples, size_t seg_stride,
+                                const wspr_waterfall_params *p /* NULL = default */,
+                                void *d_img, size_t img_stride, wspr_waterfall_info *info /* host, nseg */);
+int wspr_waterfall(const float *I, const float *Q, int samples, const wspr_waterfall_params *p,
+                   uint8_t *img /* host, nrows*ncols */, wspr_waterfall_info *info);
+void wspr_waterfall_palette(int which /* 0 grey, 1 the colour ramp */, uint8_t rgb[768]);
+int wspr_write_pgm_file(const char *filename, const uint8_t *img, int width, int height);
+int wspr_write_png_file(const char *filename, const uint8_t *img, int width, int height, const uint8_t *rgb768 /* NULL = grey */);
+
 /* ---- receiver session --------------------------------------------------------------------
  * The reference's rx_state (two I/Q buffers of 45000 samples, their fill counters, the active index,
  * rtlsdr_wsprd.c:78-90), the decimator's static state (:135-160) and the body of its decoder thread (:263-328) as

@@ -195,6 +195,21 @@ def _bind(path):
     L.wspr_noise_batch_device.restype = C.c_int
     L.wspr_noise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
     L.wspr_noise.restype = C.c_int
+    L.wspr_waterfall_default_params.argtypes = [C.c_void_p]
+    L.wspr_waterfall_default_params.restype = None
+    L.wspr_waterfall_shape.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wspr_waterfall_shape.restype = C.c_int
+    L.wspr_waterfall_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p,
+                                              C.c_size_t, C.c_void_p]
+    L.wspr_waterfall_batch_device.restype = C.c_int
+    L.wspr_waterfall.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wspr_waterfall.restype = C.c_int
+    L.wspr_waterfall_palette.argtypes = [C.c_int, C.c_void_p]
+    L.wspr_waterfall_palette.restype = None
+    L.wspr_write_pgm_file.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int]
+    L.wspr_write_pgm_file.restype = C.c_int
+    L.wspr_write_png_file.argtypes = [C.c_char_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    L.wspr_write_png_file.restype = C.c_int
     L.wspr_read_wav_file.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
     L.wspr_read_wav_file.restype = C.c_size_t
     L.wspr_write_wav_file.argtypes = [C.c_char_p, C.c_void_p, C.c_size_t]
@@ -653,6 +668,109 @@ def to_db(power):
     p = np.asarray(power, np.float64)
     with np.errstate(divide="ignore"):
         return np.where(p > 0.0, 10.0 * np.log10(np.where(p > 0.0, p, 1.0)), -np.inf)
+
+
+# include/wspr_mi355x.h: wspr_waterfall_params and wspr_waterfall_info, the waterfall of a segment (K20)
+WATERFALL_PARAMS_DTYPE = np.dtype([("hop", "<i4"), ("tavg", "<i4"), ("j0", "<i4"), ("j1", "<i4"), ("ref_mode", "<i4"),
+                                   ("ref", "<f4"), ("db_min", "<f4"), ("db_step", "<f4")])
+WATERFALL_INFO_DTYPE = np.dtype([("ref", "<f4"), ("nframes", "<i4"), ("nrows", "<i4"), ("flags", "<i4")])
+WF_REF_ABSOLUTE, WF_REF_FLOOR = 0, 1
+WF_WRITTEN, WF_NO_REF, WF_NONFINITE = 1, 2, 8
+
+
+def waterfall_default_params():
+    """wspr_waterfall_default_params() as a dict: hop, tavg, j0, j1, ref_mode, ref, db_min, db_step.  Needs no device."""
+    p = np.zeros(1, WATERFALL_PARAMS_DTYPE)
+    lib().wspr_waterfall_default_params(_ptr(p))
+    return {k: p[0][k].item() for k in WATERFALL_PARAMS_DTYPE.names}
+
+
+def _waterfall_params(params):
+    """None (the library's default), a dict that overrides some of the defaults, or a WATERFALL_PARAMS_DTYPE record, as what
+    the call takes."""
+    if params is None:
+        return None, None
+    if isinstance(params, dict):
+        d = waterfall_default_params()
+        unknown = set(params) - set(d)
+        if unknown:
+            raise KeyError("unknown waterfall parameter: %s" % sorted(unknown))
+        d.update(params)
+        p = np.zeros(1, WATERFALL_PARAMS_DTYPE)
+        for k, v in d.items():
+            p[0][k] = v
+    else:
+        p = np.array(params, WATERFALL_PARAMS_DTYPE).reshape(1)
+    return p, _ptr(p)
+
+
+def waterfall_shape(samples=NSAMPLES, params=None):
+    """wspr_waterfall_shape(): (nrows, ncols) of the image of a row of `samples` samples; raises if the library refuses the
+    parameters.  Needs no device."""
+    keep, p = _waterfall_params(params)
+    nrows, ncols = C.c_int(0), C.c_int(0)
+    rc = lib().wspr_waterfall_shape(int(samples), p, C.addressof(nrows), C.addressof(ncols))
+    if rc != 0:
+        raise ValueError("wspr_waterfall_shape refused the call (rc %d)" % rc)
+    return int(nrows.value), int(ncols.value)
+
+
+def waterfall_batch_device(d_i, d_q, nseg, samples, seg_stride, d_img, img_stride, params=None, info=None):
+    """wspr_waterfall_batch_device(): the waterfalls (K20) of nseg rows at the raw device pointers d_i / d_q (16-byte aligned,
+    seg_stride floats apart) into nseg images of waterfall_shape() bytes at the raw device pointer d_img (16-byte aligned,
+    img_stride bytes apart, a multiple of 16).  info: a WATERFALL_INFO_DTYPE array of nseg to write into, or None.  Returns
+    (rc, info): rc is the library's code (0; -1 or -2 with nothing written)."""
+    if info is None:
+        info = np.zeros(max(int(nseg), 0), WATERFALL_INFO_DTYPE)
+    keep, p = _waterfall_params(params)
+    rc = lib().wspr_waterfall_batch_device(d_i, d_q, int(nseg), int(samples), int(seg_stride), p, d_img, int(img_stride),
+                                           _ptr(info))
+    return rc, info
+
+
+def waterfall(I, Q, params=None, samples=None):
+    """wspr_waterfall(): the waterfall of one host row as (image uint8 [nrows, ncols], WATERFALL_INFO_DTYPE record); raises if
+    the library refuses the call."""
+    I = np.ascontiguousarray(I, dtype=np.float32)
+    Q = np.ascontiguousarray(Q, dtype=np.float32)
+    n = int(I.size if samples is None else samples)
+    try:
+        nrows, ncols = waterfall_shape(n, params)
+    except ValueError as e:
+        raise RuntimeError("wspr_waterfall: %s" % e) from None
+    img = np.zeros((nrows, ncols), np.uint8)
+    info = np.zeros(1, WATERFALL_INFO_DTYPE)
+    keep, p = _waterfall_params(params)
+    rc = lib().wspr_waterfall(_ptr(I), _ptr(Q), n, p, img.ctypes.data if img.size else None, _ptr(info))
+    if rc != 0:
+        raise RuntimeError("wspr_waterfall failed (rc %d: parameters out of range, more than 45000 samples, or no usable HIP "
+                           "device)" % rc)
+    return img, info[0]
+
+
+def waterfall_palette(which=1):
+    """wspr_waterfall_palette(): uint8 [256, 3], RGB of each level; 0 grey, 1 the colour ramp.  Needs no device."""
+    rgb = np.zeros((256, 3), np.uint8)
+    lib().wspr_waterfall_palette(int(which), _ptr(rgb))
+    return rgb
+
+
+def write_pgm_file(filename, img):
+    """wspr_write_pgm_file(): a uint8 image [height, width] as a binary P5 file.  Raises if it cannot be written."""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w_ = img.shape
+    if lib().wspr_write_pgm_file(os.fsencode(filename), _ptr(img), int(w_), int(h)) != 0:
+        raise OSError("wspr_write_pgm_file could not write %r" % (filename,))
+
+
+def write_png_file(filename, img, palette=None):
+    """wspr_write_png_file(): a uint8 image [height, width] as an uncompressed 8-bit PNG, grey or (palette: uint8 [256, 3])
+    indexed.  Raises if it cannot be written."""
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w_ = img.shape
+    pal = None if palette is None else np.ascontiguousarray(palette, dtype=np.uint8).reshape(768)
+    if lib().wspr_write_png_file(os.fsencode(filename), _ptr(img), int(w_), int(h), None if pal is None else _ptr(pal)) != 0:
+        raise OSError("wspr_write_png_file could not write %r" % (filename,))
 
 
 def read_wav_file(filename, cap=AUDIO_MAX_SAMPLES):

@@ -194,11 +194,11 @@ size_t Context::release_buffers() {
                               &c.lists, &c.scrsync, &c.psavg, &c.densein, &c.fz_sym, &c.fz_off, &c.fz_ret, &c.fz_cyc, &c.fz_met, &c.fz_max,
                               &c.fz_dat, &c.fz_steps, &c.fz_pool, &c.streamraw, &c.streamstate, &c.synthtx, &c.synthoff, &c.synthfirst,
                               &c.synthckpt, &c.synthrows, &c.blk_hyp, &c.blk_out, &c.spr_tw, &c.spr_jobs, &c.spr_ckpt, &c.spr_out, &c.audiopcm, &c.synthfade, &c.list_out,
-                              &c.blankrows, &c.blankcount, &c.noise_tab, &c.noise_out, &c.asynthphase, &c.asynthcount, &c.iqaudiocount,
+                              &c.blankrows, &c.blankcount, &c.noise_tab, &c.noise_out, &c.asynthphase, &c.asynthcount, &c.iqaudiocount, &c.wf_levels, &c.wf_floor, &c.wf_info, &c.wf_img,
                               &c.sq_where, &c.sq_jobs, &c.sq_out, &c.sq_keep})
                 freed += b->release();
             for (PinBuf* b : {&c.h_npk, &c.h_cand, &c.h_items, &c.h_sync, &c.h_sym, &c.h_rms, &c.h_jobs, &c.h_jobs2, &c.h_seglist,
-                              &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_sprjobs, &c.h_sprout, &c.h_sqjobs, &c.h_sqout, &c.h_noise, &c.h_list, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
+                              &c.h_misc, &c.h_lists, &c.h_fz, &c.h_blk, &c.h_sprjobs, &c.h_sprout, &c.h_sqjobs, &c.h_sqout, &c.h_noise, &c.h_wf_levels, &c.h_wf_info, &c.h_list, &c.h_stage[0], &c.h_stage[1], &c.h_streamraw, &c.h_streamstate, &c.h_streamout})
                 b->release();
             c.stage_samples[0] = c.stage_samples[1] = 0;
             free(c.hash_arena);

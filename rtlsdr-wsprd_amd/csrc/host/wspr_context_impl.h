@@ -253,7 +253,8 @@ struct Context::Impl {
         blankrows, blankcount,   // K15: at most Context::kBlankChunk blanked records on their way to K12; one counter per record
         noise_tab, noise_out,    // K16: twiddles and window (built on first use); one 32-byte record per segment
         asynthphase, asynthcount,   // K17: P_i and dphi_i of each transmission (list, offsets and first indices are K8's buffers); one counter per record
-        iqaudiocount;   // K18: one counter per record
+        iqaudiocount,   // K18: one counter per record
+        wf_levels, wf_floor, wf_info, wf_img;   // K20: the 256 thresholds of the call, K16's records of its rows (floor mode), one 16-byte record per segment, one image of wspr_waterfall()
     double noise_w2 = 0.0;       // K16: the sum of the squared window, from the same pass as the table
     PinBuf h_npk, h_cand, h_items, h_sync, h_sym, h_rms, h_jobs, h_jobs2, h_seglist, h_misc, h_lists;
     // host-buffer entry (wspr_decode_batch: the reference's calling convention, wsprd.h:106-111): pageable caller rows
@@ -270,6 +271,7 @@ struct Context::Impl {
     DevBuf spr_tw, spr_jobs, spr_ckpt, spr_out;   // K11: twiddles (built on first use), jobs, phase checkpoints, 4 words per job
     PinBuf h_sprjobs, h_sprout;      // ... the jobs on their way up, the results on their way down
     PinBuf h_noise;                  // K16: the records on their way down
+    PinBuf h_wf_levels, h_wf_info;   // K20: the thresholds on their way up, the records on their way down
     wspr_spread* spread_out = nullptr;   // where the current call's records go (the layout of its `decodes`), or null
     DevBuf sq_where, sq_jobs, sq_out, sq_keep;   // K19: the coder output at each transmission position (built on first use), [offsets | decdata] of a batch, 5 words per job, vectors a stage hands on to the bookkeeping
     PinBuf h_sqjobs, h_sqout;        // ... the jobs on their way up, the results on their way down

@@ -1,12 +1,13 @@
 // The stage calls of a context: device rows or records in, device rows or records out, outside a decode -- K0 (the
 // RTL-SDR front end and its streams), K12 (audio front end), K15 (blanker), K16 (noise figures), K8/K13 (signal
-// synthesiser), K17 (audio scene synthesiser), K18 (IQ to audio).  Each is complete on return: it ends with
+// synthesiser), K17 (audio scene synthesiser), K18 (IQ to audio), K20 (waterfall).  Each is complete on return: it ends with
 // Impl::wait() on its stream and does NOT resolve the decode's deferred timings (that is sync()).  What they share is
 // stated once, below: the staging of a transmission list and the per-record counters.  Arguments have been checked by
 // the callers (wspr_stage_args.h); contexts, buffers and loads are wspr_context.hip.
 #include "wspr_context_impl.h"
 #include "../kernels/fade.h"
 #include "../kernels/noise.h"
+#include "../kernels/waterfall.h"
 
 namespace wspr {
 
@@ -225,19 +226,25 @@ int Context::audio_blanked_device(const void* d_pcm, size_t pcm_stride, int nsam
 }
 
 // ------------------------------------------------------------------------------------------------------ K16 --
-// K16 on the lane's stream; the records come back with it.  The table is built on first use: a process that never asks
-// for the figures allocates nothing for them.
+// The table of K16 and K20 (twiddles and window) is built on first use: a process that never asks for the figures or the
+// pictures allocates nothing for them.
+namespace {
+void noise_table(Context::Impl& c) {
+    if (c.noise_tab.p) return;
+    std::vector<float> host(noise::kTableFloats);
+    const double w2 = noise::noise_tables(host.data());
+    float* p = static_cast<float*>(c.noise_tab.need(host.size() * sizeof(float)));
+    HIP_OK(hipMemcpy(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
+    c.noise_w2 = w2;
+}
+}  // namespace
+
+// K16 on the lane's stream; the records come back with it.
 int Context::noise_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, const noise::Windows& win,
                           noise::Result* out) {
     Impl& c = *d;
     if (nseg <= 0) return 0;
-    if (!c.noise_tab.p) {
-        std::vector<float> host(noise::kTableFloats);
-        const double w2 = noise::noise_tables(host.data());
-        float* p = static_cast<float*>(c.noise_tab.need(host.size() * sizeof(float)));
-        HIP_OK(hipMemcpy(p, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice));
-        c.noise_w2 = w2;
-    }
+    noise_table(c);
     const size_t bytes = (size_t)nseg * sizeof(noise::Result);
     void* d_out = c.noise_out.need(bytes);
     noise::Result* h_out = static_cast<noise::Result*>(c.h_noise.need(bytes));
@@ -248,6 +255,40 @@ int Context::noise_device(const float* dI, const float* dQ, int nseg, int sample
     memcpy(out, h_out, bytes);                               // every record has arrived before the first is handed over
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------ K20 --
+// K20 on the lane's stream: the thresholds go up, floor mode runs K16 into scratch of its own (its default windows: they
+// play no part in fft_p30), K20 reads that, the 16-byte records come down -- three steps and one wait
+int Context::waterfall_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, const waterfall::Params& p,
+                              uint8_t* d_img, size_t img_stride, waterfall::Info* info) {
+    Impl& c = *d;
+    if (nseg <= 0) return 0;
+    const hipStream_t st = c.stream;
+    noise_table(c);
+    double* h_levels = static_cast<double*>(c.h_wf_levels.need(waterfall::kLevels * sizeof(double)));
+    waterfall::level_table(p.db_min, p.db_step, h_levels);
+    double* d_levels = static_cast<double*>(c.wf_levels.need(waterfall::kLevels * sizeof(double)));
+    upload(d_levels, h_levels, waterfall::kLevels * sizeof(double), st);
+    const size_t bytes = (size_t)nseg * sizeof(waterfall::Info);
+    waterfall::Info* d_info = static_cast<waterfall::Info*>(c.wf_info.need(bytes));
+    waterfall::Info* h_info = static_cast<waterfall::Info*>(c.h_wf_info.need(bytes));
+    HIP_OK(hipMemsetAsync(d_info, 0, bytes, st));
+    noise::Result* d_floor = nullptr;
+    if (p.ref_mode == waterfall::kRefFloor) {
+        d_floor = static_cast<noise::Result*>(c.wf_floor.need((size_t)nseg * sizeof(noise::Result)));
+        launch_noise(dI, dQ, samples, stride, nseg, c.noise_tab.as<float>(), c.noise_w2,
+                     noise::Windows{noise::kPreB0, noise::kPreB1, noise::kPostB0, noise::kPostB1}, d_floor, st);
+    }
+    launch_waterfall(dI, dQ, samples, stride, nseg, c.noise_tab.as<float>(), c.noise_w2, p, d_levels, d_floor, d_img, img_stride,
+                     d_info, st);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(h_info, d_info, bytes, hipMemcpyDeviceToHost, st));
+    c.wait(st);
+    memcpy(info, h_info, bytes);                             // every record has arrived before the first is handed over
+    return 0;
+}
+
+uint8_t* Context::waterfall_image(size_t bytes) { return static_cast<uint8_t*>(d->wf_img.need(bytes + 16)); }
 
 // ---------------------------------------------------------------------------------------- K8, K13 and K17 --
 // K8, or K13 with one FadeChannel per transmission

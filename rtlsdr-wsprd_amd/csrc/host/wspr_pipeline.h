@@ -275,6 +275,12 @@ public:
     // nseg records); complete on return.  The table of twiddles and window is built on first use, as spread_twiddle_table().
     int noise_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, const noise::Windows& win,
                      noise::Result* out);
+    // K20 (k20_waterfall.hip; the definition in kernels/waterfall.h): the images of nseg validated device rows into nseg
+    // validated device images and info (host, nseg records); floor mode runs K16 into scratch of its own first, on the same
+    // stream and with no host wait in between; complete on return
+    int waterfall_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, const waterfall::Params& p,
+                         uint8_t* d_img, size_t img_stride, waterfall::Info* info);
+    uint8_t* waterfall_image(size_t bytes);   // device scratch for one image (wspr_waterfall)
 
     // The stage calls below are wspr_context_stages.hip; their arguments have been validated (wspr_stage_args.h).
     // K8 (k8_synth.hip): a validated, sorted transmission list into nseg device rows; complete on return

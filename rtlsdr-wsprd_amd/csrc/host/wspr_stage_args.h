@@ -1,4 +1,4 @@
-// What can be wrong with a stage call (K8/K13, K12, K15, K16, K17, K18, K19), each condition stated once.  Plain C++ without
+// What can be wrong with a stage call (K8/K13, K12, K15, K16, K17, K18, K19, K20), each condition stated once.  Plain C++ without
 // HIP: pointers are looked at as addresses and never dereferenced -- the transmissions, their channels and the noise
 // windows are host memory and are read.  tests/helpers/stage_args_check.cpp runs a table of calls through this header on
 // a CPU.
@@ -22,6 +22,7 @@
 #include "../kernels/fade.h"
 #include "../kernels/iq_audio.h"
 #include "../kernels/noise.h"
+#include "../kernels/waterfall.h"
 
 namespace wspr {
 namespace args {
@@ -147,6 +148,22 @@ inline int iq_audio_args_bad(const char* where, int nseg, int samples, float gai
     if (!std::isfinite(gain)) return refuse(where, "gain is not finite");
     return 0;
 }
+// K20's counts, parameters and records, the same for both calls; *use = the parameters the call uses
+inline int waterfall_args_bad(const char* where, int nseg, int samples, const wspr_waterfall_params* p, const void* info,
+                              waterfall::Params* use) {
+    *use = waterfall::default_params();
+    if (p) std::memcpy(use, p, sizeof *use);
+    if (nseg < 0 || samples < 0) return refuse(where, "negative count");
+    if (const int bad = too_long(where, samples, waterfall::kMaxSamples, kRowTooLong)) return bad;
+    if (!waterfall::hop_ok(use->hop)) return refuse(where, "hop must be 128 or 256");
+    if (!waterfall::tavg_ok(use->tavg)) return refuse(where, "tavg must be 1 .. 16");
+    if (!waterfall::bins_ok(use->j0, use->j1)) return refuse(where, "the bins must satisfy -256 <= j0 <= j1 <= 255");
+    if (!waterfall::ref_mode_ok(use->ref_mode)) return refuse(where, "unknown ref_mode");
+    if (use->ref_mode == waterfall::kRefAbsolute && !waterfall::ref_ok(use->ref)) return refuse(where, "ref must be finite and above 0");
+    if (!waterfall::levels_ok(use->db_min, use->db_step)) return refuse(where, "db_min must be -60 .. 60 and db_step 0.05 .. 4");
+    if (!info) return refuse(where, "no info records");
+    return 0;
+}
 // K17's counts, length and list, the same for both calls
 inline int synth_audio_args_bad(const char* where, const wspr_synth_tx* tx, int ntx, int nseg, long long nsamp, float sigma, int flags) {
     if (ntx < 0 || nseg < 0 || nsamp < 0) return refuse(where, "negative count");
@@ -230,6 +247,25 @@ inline int iq_audio_batch(const char* where, const void* d_i, const void* d_q, i
 inline int iq_audio_host(const char* where, const void* I, const void* Q, int samples, float gain, const void* pcm) {
     if (const int bad = iq_audio_args_bad(where, 1, samples, gain)) return bad;
     return ((!I || !Q || !pcm) && samples) ? refuse(where, "no row or no output record") : 0;
+}
+// wspr_waterfall_batch_device(): the image rows are written with aligned 16-byte vector stores
+inline int waterfall_batch(const char* where, const void* d_i, const void* d_q, int nseg, int samples, size_t seg_stride,
+                           const wspr_waterfall_params* p, const void* d_img, size_t img_stride, const void* info,
+                           waterfall::Params* use) {
+    if (const int bad = waterfall_args_bad(where, nseg, samples, p, info, use)) return bad;
+    if (const int bad = rows_bad(where, d_i, d_q, nseg)) return bad;
+    if (const int bad = row_stride_bad(where, seg_stride, samples, nseg)) return bad;
+    if (nseg > 0 && !aligned16(d_img)) return refuse(where, "d_img must be 16-byte aligned device memory");
+    const size_t need = (size_t)waterfall::rows_of(samples, use->hop, use->tavg) * (size_t)waterfall::cols_of(use->j0, use->j1);
+    if (nseg > 0 && ((img_stride & 15) || img_stride < need))
+        return refuse(where, "img_stride must be a multiple of 16 and at least nrows * ncols");
+    return 0;
+}
+inline int waterfall_host(const char* where, const void* I, const void* Q, int samples, const wspr_waterfall_params* p,
+                          const void* img, const void* info, waterfall::Params* use) {
+    if (const int bad = waterfall_args_bad(where, 1, samples, p, info, use)) return bad;
+    if ((!I || !Q) && samples) return refuse(where, "no row");
+    return (!img && waterfall::rows_of(samples, use->hop, use->tavg) > 0) ? refuse(where, "no image") : 0;
 }
 // wspr_spot_quality_batch_device() (K19): n host vectors of 162 bytes, n x 11 bytes of decdata, n records out
 inline int spot_quality_batch(const char* where, const void* symbols, const void* decdata, int n, const void* out) {

@@ -10,7 +10,7 @@
 //                 (twelve butterflies, noise.h's statements on values); between the three passes the points change
 //                 lanes through the wave's own 4.5 KB of LDS, in two padded layouts that keep the 8-byte accesses off
 //                 each other's banks: points l + 64e (stages 0-2), (l & 7) + 64 (l >> 3) + 8e (stages 3-5), 8l + e
-//                 (stages 6-8).  The windowed points come straight from the ring, the window in registers; the last
+//                 (stages 6-8); that choreography is noise_fft.h, shared with K20.  The windowed points come straight from the ring, the window in registers; the last
 //                 pass leaves output slot 8l + e in lane l, which keeps that slot's double sum in a register across all
 //                 rounds; wave w so forms the partial sum S_c of noise.h for c = (w + 3) % 4, in rising frame order.
 //                 Wave 0 forms the block powers of the round's 64 blocks that lie in a window from the same ring (one
@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include "noise.h"
+#include "noise_fft.h"
 #include "wspr_device.h"
 
 namespace wspr {
@@ -37,33 +38,10 @@ constexpr int kBlocksPerRound = kRound / noise::kBlockLen;
 static_assert(kRound == 4 * kThreads && kRound == noise::kClasses * noise::kFrameHop && kBlocksPerRound == 64, "one vector per thread, one frame per wave, one block per lane of wave 0");
 static_assert(kRing >= kRound + noise::kFft + noise::kFrameHop && (kRing & (kRing - 1)) == 0, "the ring holds the round, the frame that began before it, and what the next round writes");
 static_assert(2 * kRing * 4 == noise::kClasses * noise::kFft * 8, "the partial sums take the ring's place");
-constexpr int kExch = 568;                                 // complex points of one wave's exchange area
-// where point i lies between the first and the second pass, and between the second and the third
-__device__ __forceinline__ int pos_a(int i) { return i + 8 * (i >> 6); }
-__device__ __forceinline__ int pos_b(int i) { return (i & 7) * 65 + (i >> 3); }
-static_assert(noise::kFft - 1 + 8 * 7 < kExch && 7 * 65 + 63 < kExch, "both layouts fit");
+using noise_fft::kExch;                                    // the transform, its exchange layouts and the row loads: noise_fft.h
+using noise_fft::load_vec;
+using noise_fft::vec_non_finite;
 static_assert(noise::kClasses * kExch * 8 >= 2 * noise::kFft * 4, "the band and the band in rank order fit into the four areas");
-
-// butterfly of the points a and b of x[] with twiddle w
-__device__ __forceinline__ void bfly(float2* x, int a, int b, float2 w) {
-    noise::butterfly_values(&x[a].x, &x[a].y, &x[b].x, &x[b].y, w.x, w.y);
-}
-
-// one 16-byte vector of a row at sample a (a % 4 == 0); what lies at or behind np reads as 0 and is not touched
-__device__ __forceinline__ float4 load_vec(const float* __restrict__ row, int a, int np) {
-    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (a + 4 <= np) {
-        v = *reinterpret_cast<const float4*>(row + a);
-    } else {
-        if (a < np) v.x = row[a];
-        if (a + 1 < np) v.y = row[a + 1];
-        if (a + 2 < np) v.z = row[a + 2];
-    }
-    return v;
-}
-__device__ __forceinline__ unsigned vec_non_finite(const float4& v) {
-    return (noise::non_finite(v.x) || noise::non_finite(v.y) || noise::non_finite(v.z) || noise::non_finite(v.w)) ? 1u : 0u;
-}
 
 __global__ __launch_bounds__(kThreads)
 void noise_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, int np, size_t stride,
@@ -94,9 +72,7 @@ void noise_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
         hann[e] = table[2 * noise::kTwiddles + lane + 64 * e];
         acc[e] = 0.0;
     }
-    // the twiddles of the last pass are the same in every lane
-    const float2 w0 = make_float2(table[0], table[1]), w64 = make_float2(table[128], table[129]);
-    const float2 w128 = make_float2(table[256], table[257]), w192 = make_float2(table[384], table[385]);
+    const noise_fft::LastTwiddles last = noise_fft::last_twiddles(table);
     unsigned bad = 0;
     float4 nxtI = load_vec(rowI, 4 * tid, np), nxtQ = load_vec(rowQ, 4 * tid, np);
 
@@ -121,21 +97,8 @@ void noise_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
                 const int s = (f * noise::kFrameHop + lane + 64 * e) & (kRing - 1);
                 x[e] = make_float2(ringI[s] * hann[e], ringQ[s] * hann[e]);
             }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bfly(x, e, e + 4, tw[lane + 64 * e]);
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const float2 w = tw[(lane + 64 * e) << 1];
-                bfly(x, e, e + 2, w);
-                bfly(x, e + 4, e + 6, w);
-            }
-            {
-                const float2 w = tw[lane << 2];
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) bfly(x, e, e + 1, w);
-            }
-#pragma unroll
-            for (int e = 0; e < 8; ++e) mine[pos_a(lane + 64 * e)] = x[e];
+            noise_fft::pass_a(x, tw, lane);
+            noise_fft::store_a(mine, x, lane);
         }
         if (wave == 0) {
             const int b = r * kBlocksPerRound + lane;
@@ -154,35 +117,17 @@ void noise_kernel(const float* __restrict__ dI, const float* __restrict__ dQ, in
         }
         __syncthreads();
         if (active) {                                                     // stages 3-5 on the points lo + 64 hi + 8e
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = mine[pos_a(lo + 64 * hi + 8 * e)];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) bfly(x, e, e + 4, tw[(lo + 8 * e) << 3]);
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const float2 w = tw[(lo + 8 * e) << 4];
-                bfly(x, e, e + 2, w);
-                bfly(x, e + 4, e + 6, w);
-            }
-            {
-                const float2 w = tw[lo << 5];
-#pragma unroll
-                for (int e = 0; e < 8; e += 2) bfly(x, e, e + 1, w);
-            }
+            noise_fft::load_b(x, mine, lo, hi);
+            noise_fft::pass_b(x, tw, lo);
         }
         __syncthreads();                                                  // every lane has read what it needs of the first layout
         if (active) {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) mine[pos_b(lo + 64 * hi + 8 * e)] = x[e];
+            noise_fft::store_b(mine, x, lo, hi);
         }
         __syncthreads();
         if (active) {                                                     // stages 6-8 on the points 8l + e: the output slots
-#pragma unroll
-            for (int e = 0; e < 8; ++e) x[e] = mine[pos_b(8 * lane + e)];
-            bfly(x, 0, 4, w0); bfly(x, 1, 5, w64); bfly(x, 2, 6, w128); bfly(x, 3, 7, w192);
-            bfly(x, 0, 2, w0); bfly(x, 4, 6, w0); bfly(x, 1, 3, w128); bfly(x, 5, 7, w128);
-#pragma unroll
-            for (int e = 0; e < 8; e += 2) bfly(x, e, e + 1, w0);
+            noise_fft::load_c(x, mine, lane);
+            noise_fft::pass_c(x, last);
 #pragma unroll
             for (int e = 0; e < 8; ++e) acc[e] += (double)noise::slot_power(x[e].x, x[e].y);
         }

@@ -300,6 +300,15 @@ void launch_iq_audio(const float* dI, const float* dQ, size_t stride, int sample
 namespace noise { struct Windows; struct Result; }
 void launch_noise(const float* dI, const float* dQ, int samples, size_t stride, int nseg, const float* table, double w2,
                   const noise::Windows& win, void* out, hipStream_t st);
+// K20, the waterfall of a segment (k20_waterfall.hip; the definition in waterfall.h): rows as K16's into nseg images of
+// rows_of() x cols_of() bytes (image s at img + s * img_stride; img 16-byte aligned, img_stride a multiple of 16 and >= the
+// image; bytes behind the image left alone) and nseg records of 16 bytes (waterfall::Info) at info, which the caller has
+// ZEROED.  table, w2: K16's.  p: validated.  levels: the waterfall::kLevels doubles of waterfall::level_table() on the
+// device.  floors: K16's records of the same rows on the device (floor mode; queued before on the same stream) or null.
+namespace waterfall { struct Params; struct Info; }
+void launch_waterfall(const float* dI, const float* dQ, int samples, size_t stride, int nseg, const float* table, double w2,
+                      const waterfall::Params& p, const double* levels, const noise::Result* floors, uint8_t* img,
+                      size_t img_stride, waterfall::Info* info, hipStream_t st);
 // K14, list decoding against known messages (k14_list.hip; the definition in listmatch.h): vector i = the 162 soft symbols at
 // symbols + offsets[i] * 162 (transmission order) against the m listed code words.  table: 48 x padded(m) words of four int8
 // chips, word-major, zero beyond position 161 and beyond entry m - 1; bias: B of each entry.  ListMatch is wspr_list_match
