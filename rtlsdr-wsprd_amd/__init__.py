@@ -226,6 +226,14 @@ def _bind(path):
     L.wspr_iq_to_audio.restype = C.c_int
     L.wspr_write_c2_file.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_double]
     L.wspr_write_c2_file.restype = C.c_int
+    L.wspr_tune_step.argtypes = [C.c_double, C.c_void_p]
+    L.wspr_tune_step.restype = C.c_uint32
+    L.wspr_tune_u8_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+    L.wspr_tune_u8_batch_device.restype = C.c_int
+    L.wspr_tune_u8.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.wspr_tune_u8.restype = C.c_int
+    L.wspr_tune_constants.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.wspr_tune_constants.restype = None
     L.wspr_selftest.argtypes = [decoder_options, C.c_void_p]
     L.wspr_selftest.restype = C.c_int
     L.nhash.restype = C.c_uint32
@@ -857,6 +865,51 @@ def iq_to_audio(I, Q, gain=IQ_AUDIO_GAIN, samples=None):
         raise RuntimeError("wspr_iq_to_audio failed (rc %d: a non-finite gain, more than 45000 samples, or no usable HIP "
                            "device)" % rc)
     return pcm, int(clipped.value)
+
+
+TUNE_MAX_BANDS = 16                # include/wspr_mi355x.h: the tunable multi-band front end (K21)
+TUNE_SAMPLES_PER_OUTPUT = 6400     # 2.4 Msps in, 375.000 Hz out
+
+
+def tune_step(offset_hz):
+    """wspr_tune_step(): (the 32-bit oscillator step that brings a signal at +offset_hz of a 2.4 Msps capture to 0 Hz, the
+    offset in Hz that step stands for).  Host code: needs no device."""
+    realised = C.c_double(0.0)
+    step = lib().wspr_tune_step(float(offset_hz), C.addressof(realised))
+    return int(step), float(realised.value)
+
+
+def tune_u8_batch_device(d_raw, bytes_per_seg, nseg, steps, d_i, d_q, normalise=1):
+    """wspr_tune_u8_batch_device(): nseg rows of bytes_per_seg raw bytes at the raw device pointer d_raw (16-byte aligned,
+    bytes_per_seg a multiple of 16) and the steps of len(steps) bands (1 .. 16, of tune_step()) into nseg * len(steps) device
+    rows of wspr_iq_stride() floats at d_i / d_q: row s * nbands + b = segment s tuned by steps[b].  Returns the library's code
+    (0; -1 with nothing written)."""
+    st = None if steps is None else np.ascontiguousarray(steps, dtype=np.uint32)
+    return lib().wspr_tune_u8_batch_device(d_raw, int(bytes_per_seg), int(nseg), None if st is None else _ptr(st),
+                                           0 if st is None else int(st.size), d_i, d_q, int(normalise))
+
+
+def tune_u8(iq, steps, normalise=1):
+    """wspr_tune_u8(): one capture of unsigned-8-bit IQ bytes in host memory into len(steps) rows of 45000 floats, through the
+    device.  Returns (I, Q float32 [nbands, 45000], n_out); raises if the library refuses the call."""
+    iq = np.ascontiguousarray(iq, dtype=np.uint8)
+    st = np.ascontiguousarray(steps, dtype=np.uint32)
+    I = np.zeros((st.size, NSAMPLES), np.float32)
+    Q = np.zeros((st.size, NSAMPLES), np.float32)
+    n = C.c_uint32(0)
+    rc = lib().wspr_tune_u8(_ptr(iq), int(iq.size), _ptr(st), int(st.size), _ptr(I), _ptr(Q), C.addressof(n), int(normalise))
+    if rc != 0:
+        raise RuntimeError("wspr_tune_u8 failed (rc %d: no steps, more than 16 bands, or no usable HIP device)" % rc)
+    return I, Q, int(n.value)
+
+
+def tune_constants():
+    """wspr_tune_constants(): (C[256], F[256] as complex-valued int arrays [256, 2] of (re, im), input samples per output)."""
+    c = np.zeros(512, np.int16)
+    f = np.zeros(512, np.int16)
+    r = C.c_int(0)
+    lib().wspr_tune_constants(_ptr(c), _ptr(f), C.addressof(r))
+    return c.reshape(256, 2), f.reshape(256, 2), int(r.value)
 
 
 def write_c2_file(filename, I, Q, dial_hz):

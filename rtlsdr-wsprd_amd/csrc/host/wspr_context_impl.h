@@ -254,6 +254,7 @@ struct Context::Impl {
         noise_tab, noise_out,    // K16: twiddles and window (built on first use); one 32-byte record per segment
         asynthphase, asynthcount,   // K17: P_i and dphi_i of each transmission (list, offsets and first indices are K8's buffers); one counter per record
         iqaudiocount,   // K18: one counter per record
+        tunescratch, tuneraw,   // K21: the block sums of a call; one capture of wspr_tune_u8()
         wf_levels, wf_floor, wf_info, wf_img;   // K20: the 256 thresholds of the call, K16's records of its rows (floor mode), one 16-byte record per segment, one image of wspr_waterfall()
     double noise_w2 = 0.0;       // K16: the sum of the squared window, from the same pass as the table
     PinBuf h_npk, h_cand, h_items, h_sync, h_sym, h_rms, h_jobs, h_jobs2, h_seglist, h_misc, h_lists;

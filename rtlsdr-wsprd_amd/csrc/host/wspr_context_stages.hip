@@ -1,6 +1,6 @@
 // The stage calls of a context: device rows or records in, device rows or records out, outside a decode -- K0 (the
 // RTL-SDR front end and its streams), K12 (audio front end), K15 (blanker), K16 (noise figures), K8/K13 (signal
-// synthesiser), K17 (audio scene synthesiser), K18 (IQ to audio), K20 (waterfall).  Each is complete on return: it ends with
+// synthesiser), K17 (audio scene synthesiser), K18 (IQ to audio), K20 (waterfall), K21 (tunable front end).  Each is complete on return: it ends with
 // Impl::wait() on its stream and does NOT resolve the decode's deferred timings (that is sync()).  What they share is
 // stated once, below: the staging of a transmission list and the per-record counters.  Arguments have been checked by
 // the callers (wspr_stage_args.h); contexts, buffers and loads are wspr_context.hip.
@@ -338,6 +338,26 @@ int Context::synth_audio_device(const wspr_synth_tx* tx, int ntx, int nseg, long
     clipped.hand_over(h_clipped);
     return 0;
 }
+
+// ------------------------------------------------------------------------------------------------------ K21 --
+int Context::tune_device(const void* d_raw, size_t bytes_per_seg, int nseg, const uint32_t* steps, int nbands, float* dI, float* dQ,
+                         int normalise, int* h_nout) {
+    Impl& c = *d;
+    if (nseg <= 0) return 0;
+    const int nrows = nseg * nbands;
+    long long* scratch = static_cast<long long*>(c.tunescratch.need(tune_scratch_bytes(bytes_per_seg, nseg, nbands) + 16));
+    int* d_nv = static_cast<int*>(c.nvalid.need((size_t)nrows * 4));
+    launch_tune(static_cast<const uint8_t*>(d_raw), bytes_per_seg, nseg, steps, nbands, dI, dQ, d_nv, scratch, c.stream);
+    HIP_OK(hipGetLastError());
+    if (normalise) launch_normalise(dI, dQ, d_nv, nrows, kMaxSamples, c.stream);
+    std::vector<int> nout((size_t)nrows, 0);
+    if (h_nout) HIP_OK(hipMemcpyAsync(nout.data(), d_nv, (size_t)nrows * 4, hipMemcpyDeviceToHost, c.stream));
+    c.wait(c.stream);
+    if (h_nout) memcpy(h_nout, nout.data(), (size_t)nrows * 4);
+    return 0;
+}
+
+uint8_t* Context::tune_raw(size_t bytes) { return static_cast<uint8_t*>(d->tuneraw.need(bytes + 16)); }
 
 // ------------------------------------------------------------------------------------------------------ K18 --
 int Context::iq_audio_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, float gain, int16_t* d_pcm,

@@ -299,6 +299,12 @@ public:
     int iq_audio_device(const float* dI, const float* dQ, int nseg, int samples, size_t stride, float gain, int16_t* d_pcm,
                         size_t pcm_stride, int* h_clipped);
 
+    // K21 (k21_tune.hip; the definition in kernels/tune.h): nseg validated device rows of raw bytes and nbands validated host
+    // steps into nseg * nbands device rows; h_nout (nseg * nbands, may be null) = outputs of each; complete on return
+    int tune_device(const void* d_raw, size_t bytes_per_seg, int nseg, const uint32_t* steps, int nbands, float* dI, float* dQ,
+                    int normalise, int* h_nout);
+    uint8_t* tune_raw(size_t bytes);   // device scratch for one capture (wspr_tune_u8)
+
     struct Impl;
     struct DecodeRun;               // state of one decode_core() call (wspr_pipeline.hip)
     std::unique_ptr<Impl> d;

@@ -1,4 +1,4 @@
-// What can be wrong with a stage call (K8/K13, K12, K15, K16, K17, K18, K19, K20), each condition stated once.  Plain C++ without
+// What can be wrong with a stage call (K8/K13, K12, K15, K16, K17, K18, K19, K20, K21), each condition stated once.  Plain C++ without
 // HIP: pointers are looked at as addresses and never dereferenced -- the transmissions, their channels and the noise
 // windows are host memory and are read.  tests/helpers/stage_args_check.cpp runs a table of calls through this header on
 // a CPU.
@@ -22,6 +22,7 @@
 #include "../kernels/fade.h"
 #include "../kernels/iq_audio.h"
 #include "../kernels/noise.h"
+#include "../kernels/tune.h"
 #include "../kernels/waterfall.h"
 
 namespace wspr {
@@ -164,6 +165,13 @@ inline int waterfall_args_bad(const char* where, int nseg, int samples, const ws
     if (!info) return refuse(where, "no info records");
     return 0;
 }
+// K21's counts and steps, the same for both calls
+inline int tune_args_bad(const char* where, int nseg, const void* steps, int nbands) {
+    if (nseg < 0) return refuse(where, "negative count");
+    if (nbands < 1 || nbands > TUNE_MAX_BANDS) return refuse(where, "nbands must be 1 .. 16");
+    if (!steps) return refuse(where, "no steps");
+    return 0;
+}
 // K17's counts, length and list, the same for both calls
 inline int synth_audio_args_bad(const char* where, const wspr_synth_tx* tx, int ntx, int nseg, long long nsamp, float sigma, int flags) {
     if (ntx < 0 || nseg < 0 || nsamp < 0) return refuse(where, "negative count");
@@ -266,6 +274,18 @@ inline int waterfall_host(const char* where, const void* I, const void* Q, int s
     if (const int bad = waterfall_args_bad(where, 1, samples, p, info, use)) return bad;
     if ((!I || !Q) && samples) return refuse(where, "no row");
     return (!img && waterfall::rows_of(samples, use->hop, use->tavg) > 0) ? refuse(where, "no image") : 0;
+}
+// wspr_tune_u8_batch_device(): the raw rows are read with aligned 16-byte vector loads
+inline int tune_batch(const char* where, const void* d_raw, size_t bytes_per_seg, int nseg, const void* steps, int nbands,
+                      const void* d_i, const void* d_q) {
+    if (const int bad = tune_args_bad(where, nseg, steps, nbands)) return bad;
+    if (bytes_per_seg & 15) return refuse(where, "bytes_per_seg must be a multiple of 16");
+    if (nseg > 0 && !aligned16(d_raw)) return refuse(where, "d_raw must be 16-byte aligned device memory");
+    return rows_bad(where, d_i, d_q, nseg);
+}
+inline int tune_host(const char* where, const void* iq, size_t nbytes, const void* steps, int nbands, const void* I, const void* Q) {
+    if (const int bad = tune_args_bad(where, 1, steps, nbands)) return bad;
+    return ((!iq && nbytes) || !I || !Q) ? refuse(where, "no capture, or no output rows") : 0;
 }
 // wspr_spot_quality_batch_device() (K19): n host vectors of 162 bytes, n x 11 bytes of decdata, n records out
 inline int spot_quality_batch(const char* where, const void* symbols, const void* decdata, int n, const void* out) {

@@ -265,6 +265,14 @@ void front_end_constants(float* taps33, int* samples_per_output);   // the FIR t
 // states: null = zero state, whole blocks only; else one DecimState per segment row, read and updated
 void launch_decimate(const uint8_t* raw, size_t bytes_per_seg, int nseg, float* dI, float* dQ,
                      int* n_out, int32_t* scratch, hipStream_t st, DecimState* states = nullptr);
+// K21, the tunable multi-band front end (k21_tune.hip; the definition in tune.h): nseg rows of bytes_per_seg bytes (raw 16-byte
+// aligned, bytes_per_seg a multiple of 16) and nbands (1 .. 16) host steps into nseg * nbands rows of kIqStride floats, row
+// s * nbands + b = segment s tuned by steps[b]; the whole row written (zero from tune n_out on); n_out: one device int per
+// output row.  scratch: tune_scratch_bytes() bytes.  tune_band_tile(): bands a pass over the raw rows serves.
+int tune_band_tile();
+size_t tune_scratch_bytes(size_t bytes_per_seg, int nseg, int nbands);
+void launch_tune(const uint8_t* raw, size_t bytes_per_seg, int nseg, const uint32_t* steps, int nbands, float* dI, float* dQ,
+                 int* n_out, long long* scratch, hipStream_t st);
 // K12, the 12 kHz audio front end (k12_audio.hip; the definition in audio_front.h): nseg records of nsamp 16-bit samples
 // (row s at pcm + s * pcm_stride; pcm 16-byte aligned, pcm_stride a multiple of 8 and >= nsamp, 0 <= nsamp <= 1 440 000)
 // into rows of kIqStride floats, the whole row written (zero from min(ceil(nsamp / 32), 45000) on).
